@@ -17,6 +17,12 @@ N > 1: one process per GPU.  Either the driver starts the ranks
 `torch.distributed.run` as a child process, relays rank 0's JSON line and exits with the child's code.
 The batch shards by instance (weak scaling, no data-path collective); the scalar loss is
 all-reduced over RCCL each step.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the `--steps` steps and prints the line (`value`, `ms_per_step`, ...).
+Everything else it can measure -- the other step form, HIP-event kernel times and the roofline, the packed-store /
+training-step side measurements, the other BASELINE configs, the CPU baselines and the sharded-store leg of a
+distributed run -- runs only with `--full`.  `--dump-outputs DIR` writes the outputs of the last timed step
+(rank 0's shard) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 
 from __future__ import annotations
@@ -60,12 +66,17 @@ def parse(argv=None):
                     help="time the back-to-back form as `value`: the general dense operator, pack kernel then solve kernel "
                          "per step (what a plain `module(pred, bctr)` call launches).  Default: the fused step -- one "
                          "launch per step holds the solve of batch i and the pack of batch i+1; every timed step still "
-                         "does one pack and one solve.  The other form is timed too and reported beside it")
+                         "does one pack and one solve.  With --full the other form is timed too and reported beside it")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the RCCL process group even at --gpus 1 (world size 1) and run the per-step "
-                         "[sum loss, count] all-reduce and the sharded-store leg: the code path of an N-GPU run")
+                         "[sum loss, count] all-reduce (and, with --full, the sharded-store leg): the code path of an N-GPU run")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous / JSON-relay check without a GPU (gloo, no kernels; CPU tests)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (other step form, kernel times / roofline, packed store, "
+                         "training step, other configs, CPU baselines, sharded store); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32, at most 64 MB in all)")
     return ap.parse_args(argv)
 
 
@@ -228,6 +239,29 @@ def clarabel_baseline(ctrs_np, signed_np, k):
     return {"status": "timed", "projections_per_s_1core": k / (time.perf_counter() - t0), "max_iter": 3}
 
 
+# --------------------------------------------------------------------------- output dump
+
+DUMP_LIMIT = 64 << 20  # bytes written by --dump-outputs, all files together
+
+
+def dump_outputs(path, arrays):
+    """`arrays`: name -> host array with the instance in dimension 0.  Written as float32 .npy files; if they would
+    exceed DUMP_LIMIT, the same fixed, seeded sample of instances is kept from each (its ids in sample_rows.npy)."""
+    import numpy as np
+
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a.nbytes // max(1, len(a)) for a in arrays.values())
+    if row_bytes * n > DUMP_LIMIT:
+        keep = max(1, (DUMP_LIMIT - 4096 - 8 * n) // (row_bytes + 8))  # (4096: the .npy headers)
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 # --------------------------------------------------------------------------- main measurement
 
 def main(argv=None):
@@ -348,8 +382,54 @@ def main(argv=None):
     if use_dist:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax)
-
+    step_ms = 1e3 * dt / args.steps
     fused = bool(args.pipeline and isinstance(state["prep"], PreparedCones))
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step (its status is checked above)
+        dump_outputs(args.dump_outputs, {k: o[k].cpu().numpy() for k in outs})
+
+    res = None
+    if rank == 0:
+        res = {
+            "metric": "cone projections/sec", "value": world * B * args.steps / dt, "unit": "projections/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": step_ms,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
+            "data": "synthetic",
+            "config": {"workload": f"TSP-{args.tsp} DFJ tight cones, {args.instances} instances, batch {B}/GPU, "
+                                   f"CaVE+ ({args.mode}) solver='hip', dense (B,m_max,d) wire format, "
+                                   f"{R} rotating batches ({R * ctrs.numel() * 4 / 1e6:.0f} MB of cones per GPU)",
+                       "batch_per_gpu": B, "d": d, "m_max": m_max, "parallelism": f"dp{world}"},
+            "newton_iters_mean": float(o["iters"].float().mean()), "newton_iters_max": int(o["iters"].max()),
+            "pipeline": {"form": "fused step (one launch: solve of batch i + pack of batch i+1)" if fused else
+                         "back to back (general dense operator: pack kernel, then solve kernel)",
+                         "fused_us_per_step": 1e3 * step_ms if fused else None,
+                         "back_to_back_us_per_step": None if fused else 1e3 * step_ms,
+                         "streams": 1, "events": 0,
+                         "note": "`value` is the form named in `form` (--no-pipeline selects the other); --full times the "
+                                 "other form over the same number of steps.  The fused form needs the NEXT batch's cones "
+                                 "at the loss call: cave_amd.dataset.prefetch(loader) or loss_fn.prepare(bctr, next_bctr)"},
+        }
+        if use_dist:
+            res["process_group"] = {"backend": "nccl (RCCL)", "world_size": world,
+                                    "per_step_collective": "all_reduce([sum loss, count]), 8 bytes"}
+    if args.full:
+        full_measurements(args, res, step, state, batches, ctrs_np, costs_np, pred_np, ids, pred, ctrs, dev, mode, outs,
+                          fused, step_ms, world, rank, use_dist)
+    if rank == 0:
+        print(json.dumps(res))
+    if use_dist:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_measurements(args, res, step, state, batches, ctrs_np, costs_np, pred_np, ids, pred, ctrs, dev, mode, outs,
+                      fused, step_ms, world, rank, use_dist):
+    """--full: the side measurements of the run, added to `res` (rank 0's result line; None on the other ranks)."""
+    import numpy as np
+    import torch
+
+    R = len(batches)
+    B, m_max, d = ctrs.shape
 
     # ---- the OTHER form, timed the same way (not `value`): ADVICE r3 -- always report both
     def timed_form(use_fused, n):
@@ -404,7 +484,6 @@ def main(argv=None):
         m_i = (np.abs(ctrs_np[bids]).sum(axis=2) > 0).sum(axis=1)
         alg.append(int((4 * m_i * d).sum() + B * (4 * d + 4 * d + 4)))
     alg_bytes = int(np.mean(alg))
-    step_ms = 1e3 * dt / args.steps
     # roofline of the dominant kernel: algorithmic bytes per launch / its average launch duration, HIP events on the
     # launch stream around single launches (fused form: the step IS that one launch; the figure of the timed region,
     # launches back to back, is reported beside it)
@@ -418,38 +497,17 @@ def main(argv=None):
     except Exception:  # noqa: BLE001
         pass
     if rank == 0:
-        res = {
-            "metric": "cone projections/sec", "value": world * B * args.steps / dt, "unit": "projections/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": f"TSP-{args.tsp} DFJ tight cones, {args.instances} instances, batch {B}/GPU, "
-                                   f"CaVE+ ({args.mode}) solver='hip', dense (B,m_max,d) wire format, "
-                                   f"{R} rotating batches ({R * ctrs.numel() * 4 / 1e6:.0f} MB of cones per GPU)",
-                       "batch_per_gpu": B, "d": d, "m_max": m_max, "parallelism": f"dp{world}"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": kernels, "kernel_ms": kern_ms, "algorithmic_bytes": alg_bytes,
-                         "frac_timed_region": alg_bytes / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "kernel_ms_note": "kernel_ms: average of HIP-event times around single launches of the step "
-                                           "(rotating batches); achieved / frac = algorithmic bytes / kernel_ms; "
-                                           "frac_timed_region = algorithmic bytes / ms_per_step (launches back to back, "
-                                           "host time included); per-kernel durations: profiles/r04_kernel_stats.csv",
-                         "memory_level": f"HBM (the {R} rotating batches exceed the 256 MB Infinity Cache)" if
-                         R * ctrs.numel() * 4 > 300e6 else "may be served by the Infinity Cache (working set < 256 MB)"},
-            "newton_iters_mean": float(o["iters"].float().mean()), "newton_iters_max": int(o["iters"].max()),
-            "pipeline": {"form": "fused step (one launch: solve of batch i + pack of batch i+1)" if fused else
-                         "back to back (general dense operator: pack kernel, then solve kernel)",
-                         "fused_us_per_step": 1e3 * step_ms if fused else other_us,
-                         "back_to_back_us_per_step": other_us if fused else 1e3 * step_ms,
-                         "streams": 1, "events": 0,
-                         "note": "both forms are timed over the same number of steps; `value` is the form named in `form` "
-                                 "(--no-pipeline selects the other).  The fused form needs the NEXT batch's cones at the "
-                                 "loss call: cave_amd.dataset.prefetch(loader) or loss_fn.prepare(bctr, next_bctr)"},
-        }
-        if use_dist:
-            res["process_group"] = {"backend": "nccl (RCCL)", "world_size": world,
-                                    "per_step_collective": "all_reduce([sum loss, count]), 8 bytes"}
+        res["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                           "kernel": kernels, "kernel_ms": kern_ms, "algorithmic_bytes": alg_bytes,
+                           "frac_timed_region": alg_bytes / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                           "kernel_ms_note": "kernel_ms: average of HIP-event times around single launches of the step "
+                                             "(rotating batches); achieved / frac = algorithmic bytes / kernel_ms; "
+                                             "frac_timed_region = algorithmic bytes / ms_per_step (launches back to back, "
+                                             "host time included); per-kernel durations: profiles/r04_kernel_stats.csv",
+                           "memory_level": f"HBM (the {R} rotating batches exceed the 256 MB Infinity Cache)" if
+                           R * ctrs.numel() * 4 > 300e6 else "may be served by the Infinity Cache (working set < 256 MB)"}
+        res["pipeline"]["back_to_back_us_per_step" if fused else "fused_us_per_step"] = other_us
         # side measurements only in the single-process run: under N ranks they would keep rank 0 busy for tens of
         # seconds while the others wait in a collective
         if not args.no_extras and world == 1:
@@ -459,16 +517,11 @@ def main(argv=None):
         if args.cpu_sample > 0 and world == 1:
             res["cpu_baseline"] = cpu_baseline(ctrs_np[ids], -pred_np, args.cpu_sample, f"TSP-{args.tsp}")
             res["gpu_over_cpu_1core_nnls"] = res["value"] / res["cpu_baseline"]["value"]
-    # every rank reaches the sharded-store leg (collectives inside) right after the timed loop; rank 0 prints last
+    # every rank reaches the sharded-store leg (collectives inside); rank 0 prints last
     if use_dist:
         shard = sharded_store_leg(args, ctrs_np, costs_np, dev, mode, outs, rank, world)
         if rank == 0:
             res["sharded_packed_store"] = shard
-    if rank == 0:
-        print(json.dumps(res))
-    if use_dist:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 def sharded_store_leg(args, ctrs_np, costs_np, dev, mode, outs, rank, world):

@@ -35,3 +35,29 @@ def test_self_launch_propagates_rank_failure():
     p = _run("--gpus", "2", "--steps", "1", "--warmup", "0", "--no-extras", "--cpu-sample", "0")
     assert p.returncode != 0
     assert "metric" not in p.stdout
+
+
+def test_dump_outputs_keeps_a_fixed_sample_under_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy per output; over the size limit, the same seeded rows of every output."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    loss = np.arange(1000, dtype=np.float64)
+    grad = np.arange(1000 * 50, dtype=np.float32).reshape(1000, 50)
+    bench.dump_outputs(str(tmp_path / "all"), {"loss": loss, "grad": grad})
+    assert sorted(os.listdir(tmp_path / "all")) == ["grad.npy", "loss.npy"]
+    assert np.load(tmp_path / "all" / "loss.npy").dtype == np.float32
+    assert np.array_equal(np.load(tmp_path / "all" / "grad.npy"), grad)
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 64 << 10)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"loss": loss, "grad": grad})
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["grad.npy", "loss.npy", "sample_rows.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 10
+    rows = np.load(tmp_path / "a" / "sample_rows.npy").astype(np.int64)
+    assert 0 < len(rows) < 1000 and np.array_equal(rows, np.load(tmp_path / "b" / "sample_rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "grad.npy"), grad[rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "loss.npy"), loss[rows].astype(np.float32))

@@ -231,7 +231,7 @@ def test_bench_force_dist_single_gpu():
     barrier-bracketed timing, sharded packed store) at world size 1."""
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "5",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--full", "--steps", "5",
                         "--warmup", "2", "--cpu-sample", "0", "--instances", "1024", "--rotate", "1", "--batch", "256", "--no-extras"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -240,6 +240,37 @@ def test_bench_force_dist_single_gpu():
     res = json.loads(line[-1])
     assert res["n_gpus"] == 1 and res["value"] > 0 and res["process_group"]["world_size"] == 1
     assert res["sharded_packed_store"]["instances"] == 1024 and res["sharded_packed_store"]["projections_per_s"] > 0
+
+
+def test_bench_plain_run_dumps_last_step_outputs(tmp_path):
+    """A plain `bench.py` run times its steps and nothing else; --dump-outputs writes what the last timed step returned
+    (one rotating batch: batch 0), which the dense operator reproduces from the same seeded inputs."""
+    import torch
+
+    from cave_amd import _lib, synth
+    from cave_amd.qpsolver import cone_op_dense
+
+    env = dict(os.environ)
+    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                        "--instances", "1024", "--rotate", "1", "--batch", "256", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
+    assert len(line) == 1, r.stdout[-2000:]
+    res = json.loads(line[0])
+    assert res["steps"] == 5 and res["ms_per_step"] > 0 and res["value"] > 0
+    assert not {"roofline", "packed_store", "other_configs", "cpu_baseline"} & set(res)
+    assert sorted(os.listdir(tmp_path)) == ["grad.npy", "loss.npy"]
+    loss, grad = np.load(tmp_path / "loss.npy"), np.load(tmp_path / "grad.npy")
+    assert loss.dtype == grad.dtype == np.float32 and loss.shape == (256,) and grad.shape == (256, 190)
+
+    ctrs, costs, _ = synth.tsp_batch(20, 1024, seed=0)
+    pred = costs[:256] + np.random.default_rng(1234).normal(0, 0.05, size=costs[:256].shape).astype(np.float32)
+    o = cone_op_dense(torch.tensor(ctrs[:256], device="cuda:0"), torch.tensor(pred, device="cuda:0"), _lib.MODE_INNER,
+                      -1.0, 0.2, outputs=("loss", "grad"))
+    assert np.abs(o["loss"].cpu().numpy() - loss).max() <= 1e-5
+    assert np.abs(o["grad"].cpu().numpy() - grad).max() <= 1e-5
 
 
 def _banded_inequality_cones(B, m, width, shift, seed, pairs=0):

@@ -13,7 +13,7 @@ for r in csv.DictReader(open(fs[0])):
     wg = int(r["Workgroup_Size"]) if "Workgroup_Size" in r else int(r["Workgroup_Size_X"])
     grid = int(r["Grid_Size"]) if "Grid_Size" in r else int(r["Grid_Size_X"])
     rows[(name, grid // wg, wg)].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
-print("# rocprofv3 --kernel-trace of `python bench.py --steps 30 --warmup 5 --cpu-sample 0 --no-extras` (tools/diag/pmc_run.sh),")
+print("# rocprofv3 --kernel-trace of `python bench.py --full --steps 30 --warmup 5 --cpu-sample 0 --no-extras` (tools/diag/pmc_run.sh),")
 print("# the cone kernels split by launch shape: cone_step_kernel with 2048 workgroups = the fused step (1024 solve + 1024 pack")
 print("# blocks); with 1024 = the pack-only / solve-only launches (set-up, the back-to-back form timed beside the fused one).")
 print(f"{'kernel':58s} {'blocks':>7s} {'threads':>7s} {'calls':>6s} {'avg us':>9s} {'min us':>9s} {'max us':>9s}")

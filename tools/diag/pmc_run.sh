@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/${PROF_DIR:-prof_r04}
 mkdir -p $OUT
-CMD="python3 $R/bench.py --steps 30 --warmup 5 --cpu-sample 0 --no-extras ${BENCH_ARGS:-}"
+CMD="python3 $R/bench.py --full --steps 30 --warmup 5 --cpu-sample 0 --no-extras ${BENCH_ARGS:-}"
 pass() {  # name, rocprofv3 options...
   local name=$1; shift
   timeout -k 10 240 rocprofv3 "$@" --output-format csv -d $OUT/$name -- $CMD > $OUT/$name.json 2> $OUT/$name.err
