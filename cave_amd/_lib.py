@@ -22,7 +22,8 @@ _HEADERS = [os.path.join(_CSRC, n) for n in ("kernels.h", "cone_common.h", "cone
     [os.path.join(_ROOT, "include", "cave_hip.h")]
 # translation units: the C ABI (host code) + one file per kernel shape (cave_amd/csrc/kernels.h)
 _UNITS = ["cave_hip"] + [f"k_{op}_w{w}" for op in ("dense", "pack", "packed") for w in (1, 2, 4, 8)] + \
-    ["k_large_dense", "k_large_pack", "k_large_packed_w1", "k_large_packed_w2", "k_large_packed_w4", "k_step"]
+    ["k_large_dense", "k_large_pack", "k_large_packed_w1", "k_large_packed_w2", "k_large_packed_w4", "k_step",
+     "k_step_warm"]
 _SOURCES = [os.path.join(_CSRC, u + ".hip") for u in _UNITS] + _HEADERS
 _OBJ_DIR = os.path.join(_CSRC, "build")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
@@ -38,7 +39,7 @@ ABI_SYMBOLS = (
     "cave_hip_packed_lds_bytes",
     "cave_hip_large_slice_bytes", "cave_hip_packed_large_slice_bytes", "cave_hip_cone_dense_large",
     "cave_hip_pack_large", "cave_hip_cone_packed_large", "cave_hip_packed_large_lds_bytes", "cave_hip_packed_large_rb_bytes",
-    "cave_hip_step_lds_bytes", "cave_hip_cone_step", "cave_hip_lite_from_packed",
+    "cave_hip_step_lds_bytes", "cave_hip_cone_step", "cave_hip_lite_from_packed", "cave_hip_cone_step_warm",
 )
 
 
@@ -102,6 +103,11 @@ class LiteStore(C.Structure):
     ]
 
 
+class WarmCacheC(C.Structure):
+    """struct cave_warm_cache (include/cave_hip.h): multiplier cache of the warm fused step."""
+    _fields_ = [("n_entries", C.c_int64), ("key", C.c_void_p), ("theta", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -154,6 +160,10 @@ def load_library() -> C.CDLL:
     lib.cave_hip_cone_step.argtypes = [C.POINTER(LiteStore), vp, vp, i64, i32, f32, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp,
                                        vp, i64, i64, i64, C.POINTER(LiteStore), vp, vp, vp]
     lib.cave_hip_cone_step.restype = i32
+    lib.cave_hip_cone_step_warm.argtypes = [C.POINTER(LiteStore), vp, vp, i64, i32, f32, f32, i32, i32, vp, vp, vp, vp, vp, vp,
+                                            vp, vp, i64, i64, i64, C.POINTER(LiteStore), vp, C.POINTER(WarmCacheC), vp, vp,
+                                            vp, vp]
+    lib.cave_hip_cone_step_warm.restype = i32
     lib.cave_hip_lite_from_packed.argtypes = [C.POINTER(Store), C.POINTER(LiteStore), vp, vp]
     lib.cave_hip_lite_from_packed.restype = i32
     _lib = lib

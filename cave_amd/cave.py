@@ -23,7 +23,8 @@ import torch
 from . import _lib
 from .abcmodule import EPO, optModule, sense_sign
 from .dataset import PackedBatch
-from .qpsolver import PreparedCones, cone_op_dense, cone_op_prepared, prepare_dense
+from .qpsolver import PreparedCones, _step_qualifies, cone_op_dense, cone_op_prepared, prepare_dense
+from .warm import DEFAULT_ENTRIES, WarmCache
 
 __all__ = ["exactConeAlignedCosine", "innerConeAlignedCosine", "abstractConeAlignedCosine", "EPO", "flush_checks"]
 
@@ -42,8 +43,28 @@ def _packed_kwargs(kwargs: dict) -> dict:
 
 
 def _op_kwargs(kwargs: dict) -> dict:
-    """solver_kwargs minus the keys the loss modules consume themselves ('inner': the kind of interior point)."""
-    return {k: v for k, v in kwargs.items() if k != "inner"}
+    """solver_kwargs minus the keys the loss modules consume themselves ('inner': the kind of interior point,
+    'warm_start': the multiplier cache)."""
+    return {k: v for k, v in kwargs.items() if k not in ("inner", "warm_start")}
+
+
+_WARM_MODES = (_lib.MODE_PROJECT, _lib.MODE_EXACT, _lib.MODE_INNER)  # (HEURISTIC / AVG solve nothing; IPM runs cold)
+
+
+def _warm_dense_ok(t, kwargs: dict) -> bool:
+    """A plain dense batch the warm route may take: a shape of the fused step, launch limits not pinned by the caller
+    (cone_op_dense honours pinned waves / nnz_cap / lds_bytes; the split form of the step has none)."""
+    return not any(kwargs.get(k) for k in ("waves", "nnz_cap", "lds_bytes")) and _step_qualifies(t)
+
+
+def _warm_entries(opt) -> int:
+    """Table size for solver_kwargs['warm_start']: True = the default, an int = a capacity in distinct cones (the table
+    holds twice as many entries).  Anything else is refused."""
+    if opt is True:
+        return DEFAULT_ENTRIES
+    if isinstance(opt, int) and not isinstance(opt, bool) and opt > 0:
+        return 2 * opt
+    raise ValueError(f"Invalid solver_kwargs['warm_start'] {opt!r}. It should be True or a positive number of cones.")
 
 
 # ---- deferred status checks (solver_kwargs={"check": "lazy"})
@@ -107,22 +128,40 @@ class _ConeLossFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred_cost, tight_ctrs, mode, sign, inner_ratio, kwargs):
+        warm = kwargs.get("warm_start")  # (a WarmCache: solver_kwargs={"warm_start": ...}, see _solver_kwargs_for_call)
+        warm = warm if isinstance(warm, WarmCache) else None
         kwargs = _op_kwargs(kwargs)
         lazy = kwargs.get("check") == "lazy"
         if lazy:
             _poll_checks()  # the verdicts of earlier calls that have arrived
             kwargs = dict(kwargs, check=False)
+        if warm is not None and mode not in _WARM_MODES:
+            warm = None
+        if warm is not None and not isinstance(tight_ctrs, (PackedBatch, PreparedCones)) and _warm_dense_ok(tight_ctrs, kwargs) \
+                and tight_ctrs.device == warm.device:
+            # warm start on a plain dense batch: the split form of the fused step (pack-only launch, then solve)
+            if lazy and not _dense_shape_settled(tight_ctrs):
+                kwargs = dict(kwargs, check=True)  # first call for this shape: strict, as below
+                lazy = False
+            tight_ctrs = prepare_dense(tight_ctrs)
         if isinstance(tight_ctrs, PackedBatch):  # device-resident cones, ids only (cave_amd/dataset.py)
             o = tight_ctrs.store.cone_op(tight_ctrs.ids, pred_cost, mode, sign, inner_ratio, zero_failed=lazy,
                                          outputs=("loss", "grad"), **_packed_kwargs(kwargs))
         elif isinstance(tight_ctrs, PreparedCones):  # dense batch whose pack stage ran ahead (qpsolver.prepare_dense)
+            w = warm if warm is not None and tight_ctrs.device == warm.device else None
             o = cone_op_prepared(tight_ctrs, pred_cost, mode, sign, inner_ratio, zero_failed=lazy, outputs=("loss", "grad"),
-                                 **_packed_kwargs(kwargs))
+                                 warm=w, **_packed_kwargs(kwargs))
+            if w is not None and kwargs.get("check", True) is True:
+                from . import qpsolver
+
+                qpsolver._settled.add(tight_ctrs.shape[1:])  # a clean strict call: later lazy calls may run unchecked
         else:
             if lazy and not _dense_shape_settled(tight_ctrs):
                 kwargs = dict(kwargs, check=True)  # first call for this shape: strict, so the launch tier can settle
                 lazy = False
             o = cone_op_dense(tight_ctrs, pred_cost, mode, sign, inner_ratio, outputs=("loss", "grad"), **kwargs)
+        if warm is not None:  # diagnostics of the most recent call (device tensors): what served it, in how many iterations
+            warm.last_iters, warm.last_status, warm.last_hit = o["iters"], o["status"], o.get("warm_hit")
         loss, grad = o["loss"], o["grad"]
         if lazy:
             shape = None if isinstance(tight_ctrs, PackedBatch) else (int(tight_ctrs.shape[1]), int(tight_ctrs.shape[2]))
@@ -157,9 +196,32 @@ class abstractConeAlignedCosine(optModule):
 
     def forward(self, pred_cost: torch.Tensor, tight_ctrs: torch.Tensor) -> torch.Tensor:
         sign = sense_sign(self.optmodel.modelSense)  # ValueError on a bad sense, src/cave.py:62-67
-        loss = _ConeLossFunction.apply(pred_cost, tight_ctrs, self._mode(), sign, self._inner_ratio(),
-                                       self._solver_kwargs_for_call())
+        kwargs = self._solver_kwargs_for_call()
+        mode = self._mode()
+        if kwargs.get("warm_start"):
+            kwargs = dict(kwargs, warm_start=self._warm_cache(tight_ctrs, mode, kwargs))
+        loss = _ConeLossFunction.apply(pred_cost, tight_ctrs, mode, sign, self._inner_ratio(), kwargs)
         return self._reduce(loss)
+
+    def _warm_cache(self, tight_ctrs, mode: int, kwargs: dict) -> "WarmCache | None":
+        """The module's multiplier cache (solver_kwargs={"warm_start": ...}) when this call can use it -- a projection
+        mode on a prepared batch or a plain dense batch the fused step takes; None otherwise (a PackedBatch warm-starts
+        through its store).  Created on the device of the first call that can use it."""
+        if mode not in _WARM_MODES or isinstance(tight_ctrs, PackedBatch):
+            return None
+        if not isinstance(tight_ctrs, PreparedCones) and not (isinstance(tight_ctrs, torch.Tensor) and
+                                                              _warm_dense_ok(tight_ctrs, _op_kwargs(kwargs))):
+            return None
+        cache = getattr(self, "_warm", None)
+        if cache is None:
+            cache = self._warm = WarmCache(_warm_entries(self.solver_kwargs["warm_start"]), tight_ctrs.device)
+        return cache if cache.device == tight_ctrs.device else None
+
+    def reset_warm_start(self) -> None:
+        """Forget every cached multiplier (the next solves start cold)."""
+        cache = getattr(self, "_warm", None)
+        if cache is not None:
+            cache.reset()
 
     def _inner_ratio(self) -> float:
         return 0.0
@@ -210,6 +272,10 @@ class exactConeAlignedCosine(abstractConeAlignedCosine):
         _lib.load()  # ImportError if the HIP extension or a device is missing (cf. src/cave.py:113-117)
         self.solver = solver
         self.solver_kwargs = dict(solver_kwargs or {})
+        # warm start of the fused step (cave_amd/warm.py): True, or a capacity in distinct cones; False / absent: off
+        if self.solver_kwargs.get("warm_start", False) is not False:
+            _warm_entries(self.solver_kwargs["warm_start"])
+        self._warm = None
 
     def _mode(self) -> int:
         return _lib.MODE_EXACT

@@ -322,11 +322,19 @@ static bool lite_store_ok(const cave_lite_store* s, int64_t need, int64_t d) {
          (((uintptr_t)s->ell | (uintptr_t)s->csr16) & 15u) == 0 && ((4 * d) & 3) == 0;
 }
 
-int32_t cave_hip_cone_step(const cave_lite_store* solve, const int64_t* ids, const float* pred, int64_t B, int32_t mode, float sign,
-                           float inner_ratio, int32_t max_iter, int32_t flags, float* proj, float* rnorm, float* target, float* loss,
-                           float* grad, int32_t* status, int32_t* iters, const float* next_ctrs, int64_t B_next,
-                           int64_t m_max, int64_t d, const cave_lite_store* next, int32_t* pack_status,
-                           uint32_t* cu_tickets, void* stream) {
+static int32_t cone_step_impl(const cave_lite_store* solve, const int64_t* ids, const float* pred, int64_t B, int32_t mode,
+                              float sign, float inner_ratio, int32_t max_iter, int32_t flags, float* proj, float* rnorm,
+                              float* target, float* loss, float* grad, int32_t* status, int32_t* iters, const float* next_ctrs,
+                              int64_t B_next, int64_t m_max, int64_t d, const cave_lite_store* next, int32_t* pack_status,
+                              const cave_warm_cache* warm, const int64_t* keys, uint8_t* warm_hit, uint32_t* cu_tickets,
+                              void* stream) {
+  if (warm) {
+    const int64_t n = warm->n_entries;
+    if (n <= 0 || n >= (int64_t)1 << 40 || (n & (n - 1)) != 0)
+      return fail(CAVE_E_INVALID, "cone_step_warm: n_entries must be a power of two");
+    if (!warm->key || !warm->theta) return fail(CAVE_E_INVALID, "cone_step_warm: null key / theta array");
+    if (((uintptr_t)warm->theta & 15u) != 0) return fail(CAVE_E_INVALID, "cone_step_warm: theta must be 16-byte aligned");
+  }
   if (B < 0 || B_next < 0 || B + B_next >= (int64_t)1 << 31) return fail(CAVE_E_INVALID, "cone_step: bad batch sizes");
   if (B == 0 && B_next == 0) return CAVE_OK;
   if (d <= 0 || d > kLiteMaxD) return fail(CAVE_E_INVALID, "cone_step: need 0 < d <= 256");
@@ -355,9 +363,42 @@ int32_t cave_hip_cone_step(const cave_lite_store* solve, const int64_t* ids, con
   }
   P.lds_bytes = (uint32_t)lds;
   P.tickets = cu_tickets;
-  hipError_t e = launch_step((unsigned)(B + B_next), (uint32_t)lds, (hipStream_t)stream, P);
+  if (warm && B > 0) {  // (a pack-only launch has nothing to warm: the cold kernel)
+    StepParamsWarm PW;
+    memset(&PW, 0, sizeof(PW));
+    static_cast<StepParams&>(PW) = P;
+    PW.W.key = warm->key; PW.W.theta = warm->theta; PW.W.n = warm->n_entries; PW.W.keys = keys; PW.W.hit = warm_hit;
+    // the LDS copy of a hit's multipliers beyond both arenas, when the launch keeps its residency with it
+    const uint32_t extra = 256u;
+    if ((uint64_t)(lds + extra) * (B_next > 0 ? 6u : 4u) <= kMaxLds) { PW.W.lds_extra = extra; PW.lds_bytes += extra; }
+    hipError_t e = launch_step_warm((unsigned)(B + B_next), PW.lds_bytes, (hipStream_t)stream, PW);
+    if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch cone_step_kernel (warm)", e);
+    return CAVE_OK;
+  }
+  hipError_t e = warm_hit && B > 0 ? hipMemsetAsync(warm_hit, 0, (size_t)B, (hipStream_t)stream) : hipSuccess;
+  if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "cone_step: warm_hit", e);
+  e = launch_step((unsigned)(B + B_next), (uint32_t)lds, (hipStream_t)stream, P);
   if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch cone_step_kernel", e);
   return CAVE_OK;
+}
+
+int32_t cave_hip_cone_step(const cave_lite_store* solve, const int64_t* ids, const float* pred, int64_t B, int32_t mode, float sign,
+                           float inner_ratio, int32_t max_iter, int32_t flags, float* proj, float* rnorm, float* target, float* loss,
+                           float* grad, int32_t* status, int32_t* iters, const float* next_ctrs, int64_t B_next,
+                           int64_t m_max, int64_t d, const cave_lite_store* next, int32_t* pack_status,
+                           uint32_t* cu_tickets, void* stream) {
+  return cone_step_impl(solve, ids, pred, B, mode, sign, inner_ratio, max_iter, flags, proj, rnorm, target, loss, grad, status,
+                        iters, next_ctrs, B_next, m_max, d, next, pack_status, nullptr, nullptr, nullptr, cu_tickets, stream);
+}
+
+int32_t cave_hip_cone_step_warm(const cave_lite_store* solve, const int64_t* ids, const float* pred, int64_t B, int32_t mode,
+                                float sign, float inner_ratio, int32_t max_iter, int32_t flags, float* proj, float* rnorm,
+                                float* target, float* loss, float* grad, int32_t* status, int32_t* iters,
+                                const float* next_ctrs, int64_t B_next, int64_t m_max, int64_t d, const cave_lite_store* next,
+                                int32_t* pack_status, const cave_warm_cache* warm, const int64_t* keys, uint8_t* warm_hit,
+                                uint32_t* cu_tickets, void* stream) {
+  return cone_step_impl(solve, ids, pred, B, mode, sign, inner_ratio, max_iter, flags, proj, rnorm, target, loss, grad, status,
+                        iters, next_ctrs, B_next, m_max, d, next, pack_status, warm, keys, warm_hit, cu_tickets, stream);
 }
 
 int32_t cave_hip_lite_from_packed(const cave_cone_store* src, const cave_lite_store* dst, int32_t* status, void* stream) {

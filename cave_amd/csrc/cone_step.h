@@ -46,12 +46,54 @@ struct StepPackParams {
   int32_t* status;
 };
 
+// Multiplier cache of the warm solve half (cave_warm_cache, include/cave_hip.h): n entries of one 64-bit key and 32
+// float multipliers each, grouped in sets of min(4, n) ways.  A key hashes to one set; lanes 0..ways-1 load the set's
+// keys (ONE load) and lanes 0..31 the multipliers of all its ways beside them, so a hit costs no second round trip.
+// Keys: caller keys (the store slot of a device-resident store) carry kWarmTagId, content keys (lite_content_key: the
+// fingerprint of the cone + p, nF, non-zeros) kWarmTagContent; 0 = empty.  Plain loads and stores,
+// no atomics: a torn or stale entry is a worse starting point, never a wrong result (solve_cone_impl sanitises it and
+// the projection is unique).
+struct StepWarm {
+  uint64_t* key;         // [n]
+  float* theta;          // [n * 32]
+  int64_t n;             // entries (a power of two); the cold kernel never reads this block
+  const int64_t* keys;   // [B] caller keys, or null: the key comes from the slot's content
+  uint8_t* hit;          // [B] 1 where the instance started from cached multipliers, or null
+  uint32_t lds_extra;    // LDS bytes at the end of the launch's block kept out of both arenas (the arenas stay those of
+                         // the cold launch): the LDS copy of a hit's multipliers.  0: taken from the solve arena if room
+};
+static constexpr uint64_t kWarmTagContent = 1ull << 63, kWarmTagId = 1ull << 62;
+
 struct StepParams {
   StepSolveParams S;
   StepPackParams Q;
   uint32_t lds_bytes;   // dynamic LDS of the launch (both halves size their arenas from it)
   uint32_t* tickets;    // [4096] per-compute-unit SIMD claim masks of the wave election (caller-owned, zeroed once)
 };
+// the warm variant's kernel argument (cone_step_kernel<CP, true>): the cold one keeps its own as it was
+struct StepParamsWarm : StepParams {
+  StepWarm W;
+};
+
+// ---- fingerprint of the cone in a lite slot: a sum (mod 2^32) of one mixed term per (position, word) of the row
+// pointers and the csr16 words (what defines the reduced rows), the sign bytes of the unit rows and the count of rows
+// the projection keeps, so the per-lane partial sums may be combined in any order.  Neither the batch position nor the zero padding of the dense block (m_max) enters.  The warm solve half forms
+// it from the words its prologue loads anyway; the pack half (shared with the cold kernel) does not pay for it.
+CAVE_HOSTDEV uint32_t lite_fmix32(uint32_t h) {
+  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+  return h;
+}
+CAVE_HOSTDEV uint32_t lite_fp_term(uint32_t pos, uint32_t word) { return lite_fmix32(word ^ lite_fmix32(pos * 0x9e3779b1u + 0x7f4a7c15u)); }
+// positions of the hashed words: csr16 words 0 .. 767, row pointers, sign bytes, rows kept by the projection
+static constexpr uint32_t kLiteFpRowPos = 1u << 20, kLiteFpSignPos = 2u << 20, kLiteFpValidPos = 3u << 20;
+// the cache key of a slot: fingerprint, p, nF, non-zeros (p, nF <= 32; non-zeros <= 1536)
+CAVE_HOSTDEV uint64_t lite_content_key(uint32_t fp, int p, int nF, uint32_t nnz) {
+  return kWarmTagContent | ((uint64_t)fp << 26) | ((uint64_t)(p & 63) << 20) | ((uint64_t)(nF & 63) << 14) | (uint64_t)(nnz & 0x3fffu);
+}
+CAVE_HOSTDEV uint64_t warm_mix64(uint64_t x) {  // (splitmix64 finaliser: set index of a key)
+  x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull; x ^= x >> 27; x *= 0x94d049bb133111ebull; x ^= x >> 31;
+  return x;
+}
 
 // LDS one solve block needs for cost dimension d (reduced systems of up to 32 rows, up to 1536 non-zeros)
 static inline uint32_t step_solve_lds_bytes(int64_t d) {
@@ -205,8 +247,11 @@ CAVE_HD void run_lite_from_packed(C& c, unsigned char* smem, const LiteFromPacke
 #if defined(CAVE_GPU_CODE)
 // One wave: load slot b of the lite store into LDS (every load of the prologue is issued before the first store:
 // one memory round trip), run the one-wave Newton solver, fused epilogue.  `lane`: 0..63.
-template <class SC>
-CAVE_HD void run_lite_instance(SC& sc, unsigned char* smem, uint32_t lds_bytes, const StepSolveParams& P, int64_t b) {
+// WARM: the multiplier cache W (StepWarm) is probed before the solve and written back after it; an instance that does not
+// hit runs exactly the cold instructions from the same state (w.warm = null).
+template <class SC, bool WARM = false>
+CAVE_HD void run_lite_instance(SC& sc, unsigned char* smem, uint32_t lds_bytes, const StepSolveParams& P, int64_t b,
+                               const StepWarm& W) {
   const cave_lite_store& S = P.store;
   const int d = S.d;
   const int lane = sc.lane;
@@ -214,6 +259,7 @@ CAVE_HD void run_lite_instance(SC& sc, unsigned char* smem, uint32_t lds_bytes, 
   ar.init(smem, lds_bytes);
   int32_t st = ST_OK;
   int iters = 0;
+  bool whit = false;  // (warm variant: the solve started from cached multipliers)
   const int64_t slot_raw = P.ids ? P.ids[b] : b;
   const bool in_range = slot_raw >= 0 && slot_raw < S.n;
   const int64_t slot = in_range ? slot_raw : 0;
@@ -277,6 +323,60 @@ CAVE_HD void run_lite_instance(SC& sc, unsigned char* smem, uint32_t lds_bytes, 
     w.ldh = p | 1;
     w.H = ar.get<double>((uint32_t)(p > 0 ? p * w.ldh : 1));
     w.act = ar.get<uint8_t>(pp);
+    // ---- warm variant: probe the cache (the set's keys and the multipliers of all its ways in one round trip)
+    bool wact = false, wmatch = false;
+    int64_t went = 0;
+    uint64_t wkey = 0;
+    float wsel = 0.f;
+    if constexpr (WARM) {
+      const int64_t kraw = W.keys ? W.keys[b] : 0;
+      if (W.keys) wkey = kraw >= 0 ? ((uint64_t)kraw | kWarmTagId) : 0ull;
+      else {
+        // content key: the fingerprint of the slot's row pointers and csr16 words, from the registers the prologue
+        // loaded them into (what lies beyond the cone's own extents is not hashed: a slot is reused across batches)
+        uint32_t fpl = lane <= p ? lite_fp_term(kLiteFpRowPos + (uint32_t)lane, mp_raw) : 0u;
+        // ... and the sign bytes of the unit rows and the rows the projection keeps: cones of one problem often share
+        // their reduced rows (the TSP degree rows) and differ only in which coordinates are at a bound
+#pragma unroll
+        for (int s = 0; s < KC; ++s)
+          if (lane + 64 * s < d) fpl += lite_fp_term(kLiteFpSignPos + (uint32_t)(lane + 64 * s), uv[s]);
+        if (lane == 0) fpl += lite_fp_term(kLiteFpValidPos, (uint32_t)n_valid);
+#pragma unroll
+        for (int g8 = 0; g8 < kLiteMaxChunk / 8; ++g8)
+          if (g8 * 8 < chn8) {
+            const uint32_t q = 4u * (uint32_t)(g8 * 64 + lane);
+            fpl += lite_fp_term(q, cv[g8].x) + lite_fp_term(q + 1u, cv[g8].y) + lite_fp_term(q + 2u, cv[g8].z) +
+                   lite_fp_term(q + 3u, cv[g8].w);
+          }
+        wkey = lite_content_key(sc.reduce_add_u32(fpl), p, nF, (uint32_t)__builtin_amdgcn_readlane(hv, 2));
+      }
+      wact = need_proj && p > 0 && n_valid > 0 && wkey != 0ull;
+      if (wact) {
+        const int ways = W.n < 4 ? (int)W.n : 4;
+        // set and home way: caller keys (store slots: dense from 0) map directly -- slot k to way k % ways of set k / ways,
+        // so n slots never collide in a cache of n entries or more; content keys are hashed
+        const uint64_t mix = W.keys ? (((uint64_t)kraw / (uint64_t)ways) | ((uint64_t)kraw % (uint64_t)ways) << 32) : warm_mix64(wkey);
+        const int64_t base = (int64_t)(mix & (uint64_t)(W.n / ways - 1)) * ways;
+        const uint64_t kl = lane < ways ? W.key[base + lane] : 0ull;
+        float wt[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) wt[j] = (lane < 32 && j < ways) ? W.theta[(base + j) * 32 + lane] : 0.f;
+        const uint64_t hitm = __ballot(lane < ways && kl == wkey), freem = __ballot(lane < ways && kl == 0ull);
+        // a miss takes the first free way from the key's own "home" way on (keys of one set that miss in the same launch
+        // see the same free ways: starting from way 0 they would all take the same one, and all but one be lost), a full
+        // set loses its home way
+        const uint32_t home = (uint32_t)(mix >> 32) & (uint32_t)(ways - 1), wmask = (1u << ways) - 1u;
+        int way;
+        if (hitm) { wmatch = true; way = __ffsll((unsigned long long)hitm) - 1; }
+        else if (freem) {
+          const uint32_t f = (uint32_t)freem & wmask, rot = ((f >> home) | (f << (ways - home))) & wmask;
+          way = (int)((home + (uint32_t)(__ffs(rot) - 1)) & (uint32_t)(ways - 1));
+        } else way = (int)home;
+        went = base + way;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) wsel = j == way ? wt[j] : wsel;
+      }
+    }
     if (ar.ovf || !ell || !csr16) st = ST_TOO_LARGE;
     else {
       // ---- the LDS stores of what the prologue loaded
@@ -316,13 +416,22 @@ CAVE_HD void run_lite_instance(SC& sc, unsigned char* smem, uint32_t lds_bytes, 
       const int nI = p - nF;
       const uint32_t need = (uint32_t)(p * nI + nI * (nI | 1) + 4 * nI + (nI + 7) / 8);
       double* scr = need <= (uint32_t)d ? w.q : ar.try_get<double>(need);
+      // (warm: the hit's multipliers in LDS -- lane i < 32 stores theta_i and the solver's lane i reads it back: no sync --
+      //  beyond the arena, or after every cold allocation: a miss sees the arena of the cold kernel; no room = a miss)
+      float* wbuf = nullptr;
+      if constexpr (WARM) {
+        if (wmatch && scr)
+          wbuf = W.lds_extra >= 128u ? reinterpret_cast<float*>(smem + lds_bytes) : ar.try_get<float, 16u>(32u);
+        if (wbuf && lane < 32) wbuf[lane] = wsel;
+      }
+      bool solved = false;
       if (need_proj && !empty && !scr) st = ST_TOO_LARGE;
       else if (need_proj && !empty) {
         w.ls_on = true;
         w.ls_nF = nF;
         w.ls_nI = nI;
         w.ls_scr = scr;
-        w.warm = nullptr;
+        w.warm = wbuf;
         w.bw = 0; w.band_wave = false; w.band_hot = false; w.bwin = nullptr; w.bfac = nullptr; w.bz = nullptr; w.bstg = nullptr; w.bch = 0;
         w.dn.on = false;
         w.gen.on = false;
@@ -331,6 +440,17 @@ CAVE_HD void run_lite_instance(SC& sc, unsigned char* smem, uint32_t lds_bytes, 
         st = r.status;
         f = r.f;
         iters = r.iters;
+        solved = true;
+      }
+      if constexpr (WARM) {
+        // write-back: the final multipliers after a converged solve; a failed instance clears the entry it matched
+        if (wact && solved && st == ST_OK) {
+          if (lane < 32) W.theta[went * 32 + lane] = lane < p ? (float)w.theta[lane] : 0.f;
+          if (lane == 0) W.key[went] = wkey;
+        } else if (wact && wmatch && st != ST_OK && lane == 0) {
+          W.key[went] = 0ull;
+        }
+        whit = wbuf != nullptr;
       }
       if (st != ST_BAD_INPUT && st != ST_TOO_LARGE) {
         EpilogueOut eo;
@@ -352,6 +472,9 @@ CAVE_HD void run_lite_instance(SC& sc, unsigned char* smem, uint32_t lds_bytes, 
   if (lane == 0) {
     if (P.o.status) P.o.status[b] = st;
     if (P.o.iters) P.o.iters[b] = iters;
+    if constexpr (WARM) {
+      if (W.hit) W.hit[b] = whit ? 1 : 0;
+    }
   }
 }
 #endif  // CAVE_GPU_CODE

@@ -17,5 +17,6 @@
 namespace cave {
 using CtxStep = BlockCtx<2, true>;  // pack half: two waves per instance, 256-register budget
 CAVE_DEFINE_LAUNCH(launch_step, StepParams, cone_step_kernel<CtxStep>, CtxStep::NT)
+// (the warm variant, multiplier cache: k_step_warm.hip -- a code object of its own, the cold one stays as it was)
 CAVE_DEFINE_LAUNCH(launch_lite_from_packed, LiteFromPackedParams, lite_from_packed_kernel<Ctx2>, Ctx2::NT)
 }  // namespace cave

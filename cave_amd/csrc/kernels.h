@@ -208,10 +208,20 @@ __device__ __forceinline__ void step_release(uint32_t* masks, uint32_t claim) {
 #ifndef CAVE_STEP_SOLVE_PRIO
 #define CAVE_STEP_SOLVE_PRIO 0
 #endif
-template <class CP>
-__global__ __launch_bounds__(CP::NT, 2) void cone_step_kernel(StepParams P) {
+// WARM: the solve half reads and writes the multiplier cache P.W (cone_step.h StepParamsWarm); both halves keep the
+// arenas of the cold kernel (P.W.lds_extra bytes at the end of the block are the warm solve's own)
+template <bool WARM> struct StepArg { using type = StepParams; };
+template <> struct StepArg<true> { using type = StepParamsWarm; };
+template <class CP, bool WARM = false>
+__global__ __launch_bounds__(CP::NT, 2) void cone_step_kernel(typename StepArg<WARM>::type P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int64_t b = blockIdx.x;
+  uint32_t lds_bytes = P.lds_bytes;
+  StepWarm W{};
+  if constexpr (WARM) {
+    W = P.W;
+    lds_bytes -= W.lds_extra;
+  }
   if (b < P.S.B) {
     uint32_t claim = 0;
     const int sel = step_elect_wave<CP::NWAVES>(smem, P.tickets, claim);
@@ -225,7 +235,7 @@ __global__ __launch_bounds__(CP::NT, 2) void cone_step_kernel(StepParams P) {
     sc.st = stamps;
     unsigned long long mt0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
 #endif
-    run_lite_instance(sc, smem + kStepElectBytes, P.lds_bytes - kStepElectBytes, P.S, b);
+    run_lite_instance<SoloCtx<32, 4>, WARM>(sc, smem + kStepElectBytes, lds_bytes - kStepElectBytes, P.S, b, W);
     if (sc.lane == 0) step_release(P.tickets, claim);
 #ifdef CAVE_STAMPS
     stamps[14] = __builtin_amdgcn_s_memtime() - mt0;
@@ -249,7 +259,7 @@ __global__ __launch_bounds__(CP::NT, 2) void cone_step_kernel(StepParams P) {
   for (int i = 0; i < 32; ++i) c.st[i] = 0;
   unsigned long long mt0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
 #endif
-  if (q < P.Q.B) run_pack_lite_instance(c, smem, P.lds_bytes, P.Q, q);
+  if (q < P.Q.B) run_pack_lite_instance(c, smem, lds_bytes, P.Q, q);
 #ifdef CAVE_STAMPS
   c.st[14] = __builtin_amdgcn_s_memtime() - mt0;
   c.st[15] = rt0;
@@ -293,6 +303,7 @@ CAVE_DECL_LAUNCH_LARGE(launch_packed_large_w1, PackedParams);
 CAVE_DECL_LAUNCH_LARGE(launch_packed_large_w2, PackedParams);
 CAVE_DECL_LAUNCH_LARGE(launch_packed_large_w4, PackedParams);
 CAVE_DECL_LAUNCH(launch_step, StepParams);
+CAVE_DECL_LAUNCH(launch_step_warm, StepParamsWarm);
 CAVE_DECL_LAUNCH(launch_lite_from_packed, LiteFromPackedParams);
 
 template <class K>

@@ -308,6 +308,12 @@ class ConeStore:
             R = int(self.t["row_off"][-1])
             self.t["warm_theta"] = torch.zeros(max(R, 1), dtype=torch.float32, device=self.device)
             self.t["warm_state"] = torch.zeros(max(self.n, 1), dtype=torch.uint8, device=self.device)
+        if on and getattr(self, "lite_slots", None) is not None and getattr(self, "lite_warm", None) is None:
+            # batches served from the lite slots (<= 2048 ids) warm-start through the step kernel's multiplier cache,
+            # keyed by store slot; the per-row arrays above serve the general and large-cone paths
+            from .warm import WarmCache
+
+            self.lite_warm = WarmCache.for_capacity(self.n, self.device)
         self.warm_start = bool(on)
         self._c.warm_theta = self.t["warm_theta"].data_ptr() if on else None
         self._c.warm_state = self.t["warm_state"].data_ptr() if on else None
@@ -316,10 +322,15 @@ class ConeStore:
         """Forget every cached multiplier (the next projections start cold)."""
         if "warm_state" in self.t:
             self.t["warm_state"].zero_()
+        lw = getattr(self, "lite_warm", None)
+        if lw is not None:
+            lw.reset()
 
     def nbytes(self) -> int:
         rb = getattr(self, "rb_cache", None)
-        return sum(v.numel() * v.element_size() for v in self.t.values()) + (rb.numel() if rb is not None else 0)
+        lw = getattr(self, "lite_warm", None)
+        return sum(v.numel() * v.element_size() for v in self.t.values()) + (rb.numel() if rb is not None else 0) + \
+            (lw.nbytes if lw is not None else 0)
 
     def algorithmic_bytes(self, ids: torch.Tensor) -> int:
         """Bytes one projection pass must touch for these instances: packed rows + y in, proj/rnorm out
@@ -370,12 +381,13 @@ class ConeStore:
                     _lib.ptr(out.get("loss")), _lib.ptr(out.get("grad")), _lib.ptr(status), _lib.ptr(iters),
                     _lib.current_stream())
                 _lib.check(rc, "cave_hip_cone_packed_large")
-            elif (self.lite_slots is not None and B <= 2048 and mode != _lib.MODE_INNER_IPM and not self.warm_start
-                  and self.waves == 0):
+            elif (self.lite_slots is not None and B <= 2048 and mode != _lib.MODE_INNER_IPM and self.waves == 0
+                  and (not self.warm_start or getattr(self, "lite_warm", None) is not None)):
                 from .qpsolver import _launch_step
 
+                # (warm start: the multiplier cache keyed by store slot; out["warm_hit"] marks the instances that hit)
                 _launch_step(self.lite_slots, pred, B, mode, sign, inner_ratio, max_iter, out, status, iters, None, None, ids=ids,
-                             zero_failed=zero_failed)
+                             zero_failed=zero_failed, warm=self.lite_warm if self.warm_start else None, keys=ids)
                 if zero_failed:
                     out["zero_failed"] = True
             else:

@@ -269,18 +269,27 @@ def _step_qualifies(t) -> bool:
 
 
 def _launch_step(solve, pred, B, mode, sign, inner_ratio, max_iter, out, status, iters, nxt_ctrs, nxt_store, ids=None,
-                 zero_failed=False):
+                 zero_failed=False, warm=None, keys=None):
+    """One launch of the step kernel.  `warm` (a cave_amd.warm.WarmCache): the warm variant, which starts each solve from
+    the cache's multipliers for its key -- `keys` [B] int64, or None: the content of the cone -- and writes the
+    final ones back; out["warm_hit"] [B] uint8 then tells which instances hit."""
     lib = _lib.load()
     Bn, mn, dn = (nxt_ctrs.shape if nxt_ctrs is not None else (0, 0, solve.d))
     dev = status.device if status is not None else nxt_ctrs.device
-    rc = lib.cave_hip_cone_step(
-        solve.ref if solve is not None else None, _lib.ptr(ids), _lib.ptr(pred), B, int(mode), float(sign), float(inner_ratio),
-        int(max_iter), 1 if zero_failed else 0,
-        _lib.ptr(out.get("proj")), _lib.ptr(out.get("rnorm")), _lib.ptr(out.get("target")), _lib.ptr(out.get("loss")),
-        _lib.ptr(out.get("grad")), _lib.ptr(status), _lib.ptr(iters),
-        _lib.ptr(nxt_ctrs), Bn, mn, dn, nxt_store.ref if nxt_store is not None else None,
-        _lib.ptr(nxt_store.pack_status) if nxt_store is not None else None, _lib.ptr(_tickets_for(dev)), _lib.current_stream())
-    _lib.check(rc, "cave_hip_cone_step")
+    args = (solve.ref if solve is not None else None, _lib.ptr(ids), _lib.ptr(pred), B, int(mode), float(sign), float(inner_ratio),
+            int(max_iter), 1 if zero_failed else 0,
+            _lib.ptr(out.get("proj")), _lib.ptr(out.get("rnorm")), _lib.ptr(out.get("target")), _lib.ptr(out.get("loss")),
+            _lib.ptr(out.get("grad")), _lib.ptr(status), _lib.ptr(iters),
+            _lib.ptr(nxt_ctrs), Bn, mn, dn, nxt_store.ref if nxt_store is not None else None,
+            _lib.ptr(nxt_store.pack_status) if nxt_store is not None else None)
+    if warm is None:
+        rc = lib.cave_hip_cone_step(*args, _lib.ptr(_tickets_for(dev)), _lib.current_stream())
+        _lib.check(rc, "cave_hip_cone_step")
+        return
+    hit = out["warm_hit"] = torch.empty(B, dtype=torch.uint8, device=dev)
+    rc = lib.cave_hip_cone_step_warm(*args, warm.ref, _lib.ptr(keys), _lib.ptr(hit), _lib.ptr(_tickets_for(dev)),
+                                     _lib.current_stream())
+    _lib.check(rc, "cave_hip_cone_step_warm")
 
 
 def prepare_dense(tight_ctrs: torch.Tensor) -> "PreparedCones | torch.Tensor":
@@ -300,11 +309,12 @@ def prepare_dense(tight_ctrs: torch.Tensor) -> "PreparedCones | torch.Tensor":
 
 def cone_op_prepared(prep: PreparedCones, pred_cost: torch.Tensor, mode: int, sign: float = 1.0, inner_ratio: float = 0.2, *,
                      max_iter: int = 0, check: bool = True, zero_failed: bool = False,
-                     outputs: tuple[str, ...] = ("proj", "rnorm")) -> dict[str, torch.Tensor]:
+                     outputs: tuple[str, ...] = ("proj", "rnorm"), warm=None, keys=None) -> dict[str, torch.Tensor]:
     """The solve stage for a prepared batch (same outputs as cone_op_dense) and, in the same launch, the pack stage of
     the batch attached with `prep.then(...)`, whose PreparedCones is left in `prep.next`.  A batch with a cone the lite
     form does not take falls back to cone_op_dense on the dense tensor (checked calls only; unchecked calls report
-    CAVE_ST_TOO_LARGE in `status`)."""
+    CAVE_ST_TOO_LARGE in `status`).  `warm` (cave_amd.warm.WarmCache on this device) / `keys` ([B] int64 or None:
+    keyed by cone content): warm start from the cache, out["warm_hit"] says where it hit (the fallbacks run cold)."""
     _lib.load()
     B, m, d = prep.shape
     dev = prep.ctrs.device
@@ -332,8 +342,10 @@ def cone_op_prepared(prep: PreparedCones, pred_cost: torch.Tensor, mode: int, si
                 prep.next = PreparedCones(nctrs, nstore, nstore.gen)
             else:
                 prep.next = follow
+        if keys is not None and (keys.device != dev or keys.dtype != torch.int64 or not keys.is_contiguous()):
+            keys = keys.to(device=dev, dtype=torch.int64).contiguous()
         _launch_step(prep.store, pred, B, mode, sign, inner_ratio, max_iter, out, status, iters, nctrs, nstore,
-                     zero_failed=zero_failed)
+                     zero_failed=zero_failed, warm=warm, keys=keys)
         if zero_failed:
             out["zero_failed"] = True  # (the kernel wrote loss 0 / gradient 0 for instances whose status is not OK)
         if check:

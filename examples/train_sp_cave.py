@@ -40,7 +40,8 @@ def main(argv=None):
                          "'ipm' (truncated interior-point iterate, as the reference's Clarabel max_iter=3: src/cave.py:213-214)")
     ap.add_argument("--max-iter", type=int, default=3, help="interior-point steps of --inner ipm")
     ap.add_argument("--warm-start", action="store_true",
-                    help="(with --packed) start each projection from the multipliers of the previous epoch")
+                    help="start each projection from the multipliers of the previous epoch (packed store, or dense cones "
+                         "through solver_kwargs={'warm_start': True})")
     ap.add_argument("--graph", action="store_true",
                     help="(with --packed, not hybrid) capture predictor + loss + backward + Adam of a full batch in ONE HIP "
                          "graph and replay it per step (the C-ABI launch path allocates nothing and never syncs when the "
@@ -78,6 +79,8 @@ def main(argv=None):
         kw["check"] = False   # (a captured step cannot read the status back; it is examined after each replay below)
     elif args.lazy_check:
         kw["check"] = "lazy"
+    if args.warm_start and not args.packed:
+        kw["warm_start"] = True   # dense cones: the loss module's multiplier cache, keyed by cone content
     if args.variant == "exact":
         cave = exactConeAlignedCosine(_Model(), solver="hip", solver_kwargs=kw or None)
     elif args.variant == "inner":
@@ -158,9 +161,11 @@ def main(argv=None):
     print(f"epoch 0: regret {hist[0][2] * 100:.2f}%")
     t0 = time.time()
     iters_log = []
+    hit_log = []   # dense cones with --warm-start: share of the epoch's instances that started from cached multipliers
     for epoch in range(1, args.epochs + 1):
         tot = 0.0
         it_sum, it_max, it_n = 0.0, 0, 0
+        hit_sum, hit_n = 0.0, 0
         for x, c, cones in (prefetch(loader) if args.prefetch and not args.packed else loader):
             if graph is not None and len(x) == args.batch:
                 gx.copy_(x, non_blocking=True)
@@ -177,16 +182,23 @@ def main(argv=None):
                 loss.backward()
                 opt.step()
             tot += float(loss.detach()) * len(x)
-            if store is not None and getattr(store, "last_iters", None) is not None:
-                li = store.last_iters
+            src = store if store is not None else getattr(cave, "_warm", None)
+            if store is None and src is not None and src.last_hit is not None:
+                hit_sum, hit_n = hit_sum + float(src.last_hit.float().sum()), hit_n + src.last_hit.numel()
+            if src is not None and getattr(src, "last_iters", None) is not None:
+                li = src.last_iters
                 it_sum, it_max, it_n = it_sum + float(li.sum()), max(it_max, int(li.max())), it_n + li.numel()
         hist.append((epoch, tot / len(dataset), regret()))
         extra = ""
         if it_n:
             iters_log.append((it_sum / it_n, it_max))
             extra = f"  Newton iterations mean {it_sum / it_n:.2f} max {it_max}"
+        if hit_n:
+            hit_log.append(hit_sum / hit_n)
+            extra += f"  warm hits {100 * hit_sum / hit_n:.0f}%"
         print(f"epoch {epoch}: loss {hist[-1][1]:.4f}  regret {hist[-1][2] * 100:.2f}%{extra}")
     main.iters_log = iters_log
+    main.hit_log = hit_log
     print(f"training time {time.time() - t0:.2f} s ({args.epochs} epochs, {len(dataset)} instances, batch {args.batch})")
     return hist
 

@@ -299,6 +299,39 @@ int32_t cave_hip_cone_step(const cave_lite_store* solve, const int64_t* ids, con
                            int64_t m_max, int64_t d, const cave_lite_store* next, int32_t* pack_status,
                            uint32_t* cu_tickets, void* stream);
 
+/* ------------------------------------------------------------------ warm start of the fused step (additive to v10)
+ * Cones are static per instance and predictions drift slowly during training, so the multipliers a solve of a cone
+ * ended with are a good starting point for the next solve of the same cone (TSP-20: ~2.6 instead of ~5.2 Newton
+ * iterations).  cave_warm_cache: caller-owned device memory, a set-associative table of min(4, n_entries) ways per
+ * set; entry e holds key[e] and the 32 multipliers theta[32 e .. 32 e + 31].  Keys: the caller's keys[b] (>= 0, e.g. the
+ * store slot of a device-resident store), or, when keys is NULL, the content of the cone (a fingerprint of its row
+ * pointers, csr16 words, sign bytes and count of rows kept -- the same cone gives the same value at any batch position
+ * and any m_max -- with p, nF and the non-zero count; formed by the solve half, hdr[7] stays spare): dense batches
+ * need no ids and may be shuffled.  The two key spaces carry different tag
+ * bits.  Entries are read and written with plain loads and stores: cached multipliers are only a starting point, so a
+ * stale or torn entry costs iterations, never correctness (the projection is unique). */
+typedef struct cave_warm_cache {
+  int64_t n_entries; /* power of two */
+  uint64_t* key;     /* [n_entries], 0 = empty; zeroed by the caller (zeroing it resets the cache) */
+  float* theta;      /* [n_entries * 32], 16-byte aligned */
+} cave_warm_cache;
+
+/* cave_hip_cone_step with a multiplier cache; the parameters of cave_hip_cone_step in the same order, with
+ *   warm      the cache, or NULL: exactly cave_hip_cone_step
+ *   keys      [B] cache keys (>= 0; a negative key: no cache for that instance), or NULL: keys from the cone content
+ *   warm_hit  [B] or NULL: 1 where the instance started from cached multipliers, else 0
+ * inserted before cu_tickets.  Modes PROJECT / EXACT / INNER look up and write back (after CAVE_ST_OK: the final
+ * multipliers; after any other status the entry the instance matched is cleared); HEURISTIC / AVG do not touch the
+ * cache.  An instance that does not hit computes exactly what cave_hip_cone_step computes (outputs, status, iters).
+ * A cache whose n_entries is not a power of two, with a NULL array or a theta that is not 16-byte aligned:
+ * CAVE_E_INVALID. */
+int32_t cave_hip_cone_step_warm(const cave_lite_store* solve, const int64_t* ids, const float* pred, int64_t B, int32_t mode,
+                                float sign, float inner_ratio, int32_t max_iter, int32_t flags, float* proj, float* rnorm,
+                                float* target, float* loss, float* grad, int32_t* status, int32_t* iters,
+                                const float* next_ctrs, int64_t B_next, int64_t m_max, int64_t d, const cave_lite_store* next,
+                                int32_t* pack_status, const cave_warm_cache* warm, const int64_t* keys, uint8_t* warm_hit,
+                                uint32_t* cu_tickets, void* stream);
+
 /* Device-resident stores: cones are static per instance (src/dataset.py:72), so a packed store whose cones qualify
  * builds the lite slots of ALL its instances once (slot i of `dst` from slot i of `src`, dst->n >= src->n) and then
  * serves batches of ids through the solve half of cave_hip_cone_step (no pack half).  status [src->n] or NULL:
