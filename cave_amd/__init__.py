@@ -10,7 +10,8 @@ device is missing.
 
 from .abcmodule import EPO  # noqa: F401
 
-__all__ = ["EPO", "exactConeAlignedCosine", "innerConeAlignedCosine", "project_hip", "average_ctrs_hip"]
+__all__ = ["EPO", "exactConeAlignedCosine", "innerConeAlignedCosine", "project_hip", "average_ctrs_hip",
+           "SparseCones", "collate_sparse", "cone_op_sparse", "project_hip_sparse", "ConeStore"]
 
 
 def __getattr__(name):  # lazy: keep `import cave_amd` free of torch/ctypes side effects
@@ -18,8 +19,16 @@ def __getattr__(name):  # lazy: keep `import cave_amd` free of torch/ctypes side
         from . import cave
 
         return getattr(cave, name)
-    if name in ("project_hip", "average_ctrs_hip", "cone_op_dense", "HipSolverError"):
+    if name in ("project_hip", "average_ctrs_hip", "cone_op_dense", "HipSolverError", "cone_op_sparse", "project_hip_sparse"):
         from . import qpsolver
 
         return getattr(qpsolver, name)
+    if name in ("SparseCones", "collate_sparse"):
+        from . import sparse
+
+        return getattr(sparse, name)
+    if name == "ConeStore":
+        from .dataset import ConeStore
+
+        return ConeStore
     raise AttributeError(name)

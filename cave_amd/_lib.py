@@ -23,7 +23,7 @@ _HEADERS = [os.path.join(_CSRC, n) for n in ("kernels.h", "cone_common.h", "cone
 # translation units: the C ABI (host code) + one file per kernel shape (cave_amd/csrc/kernels.h)
 _UNITS = ["cave_hip"] + [f"k_{op}_w{w}" for op in ("dense", "pack", "packed") for w in (1, 2, 4, 8)] + \
     ["k_large_dense", "k_large_pack", "k_large_packed_w1", "k_large_packed_w2", "k_large_packed_w4", "k_step",
-     "k_step_warm"]
+     "k_step_warm", "k_pack_sparse_w2", "k_pack_sparse_w4", "k_pack_sparse_w8", "k_large_pack_sparse"]
 _SOURCES = [os.path.join(_CSRC, u + ".hip") for u in _UNITS] + _HEADERS
 _OBJ_DIR = os.path.join(_CSRC, "build")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
@@ -40,6 +40,7 @@ ABI_SYMBOLS = (
     "cave_hip_large_slice_bytes", "cave_hip_packed_large_slice_bytes", "cave_hip_cone_dense_large",
     "cave_hip_pack_large", "cave_hip_cone_packed_large", "cave_hip_packed_large_lds_bytes", "cave_hip_packed_large_rb_bytes",
     "cave_hip_step_lds_bytes", "cave_hip_cone_step", "cave_hip_lite_from_packed", "cave_hip_cone_step_warm",
+    "cave_hip_pack_count_sparse", "cave_hip_pack_fill_sparse", "cave_hip_pack_large_sparse",
 )
 
 
@@ -108,6 +109,12 @@ class WarmCacheC(C.Structure):
     _fields_ = [("n_entries", C.c_int64), ("key", C.c_void_p), ("theta", C.c_void_p)]
 
 
+class SparseConesC(C.Structure):
+    """struct cave_sparse_cones (include/cave_hip.h): a batch of cones in coordinate form."""
+    _fields_ = [("B", C.c_int64), ("m_max", C.c_int32), ("d", C.c_int32),
+                ("ent_off", C.c_void_p), ("key", C.c_void_p), ("val", C.c_void_p)]
+
+
 _lib = None
 
 
@@ -166,6 +173,11 @@ def load_library() -> C.CDLL:
     lib.cave_hip_cone_step_warm.restype = i32
     lib.cave_hip_lite_from_packed.argtypes = [C.POINTER(Store), C.POINTER(LiteStore), vp, vp]
     lib.cave_hip_lite_from_packed.restype = i32
+    lib.cave_hip_pack_count_sparse.argtypes = [C.POINTER(SparseConesC), i32, i32, i32, vp, vp, vp, vp]
+    lib.cave_hip_pack_fill_sparse.argtypes = [C.POINTER(SparseConesC), i32, i32, i32, C.POINTER(Store), i64, vp, vp]
+    lib.cave_hip_pack_large_sparse.argtypes = [C.POINTER(SparseConesC), i64, vp, i64, i32, vp, vp, C.POINTER(Store), i64, vp, vp]
+    for name in ("cave_hip_pack_count_sparse", "cave_hip_pack_fill_sparse", "cave_hip_pack_large_sparse"):
+        getattr(lib, name).restype = C.c_int32
     _lib = lib
     return lib
 

@@ -23,7 +23,8 @@ import torch
 from . import _lib
 from .abcmodule import EPO, optModule, sense_sign
 from .dataset import PackedBatch
-from .qpsolver import PreparedCones, _step_qualifies, cone_op_dense, cone_op_prepared, prepare_dense
+from .qpsolver import PreparedCones, _step_qualifies, cone_op_dense, cone_op_prepared, cone_op_sparse, prepare_dense
+from .sparse import SparseCones
 from .warm import DEFAULT_ENTRIES, WarmCache
 
 __all__ = ["exactConeAlignedCosine", "innerConeAlignedCosine", "abstractConeAlignedCosine", "EPO", "flush_checks"]
@@ -87,7 +88,7 @@ def _examine(host, what, shape) -> None:
         return
     if shape is not None and bool((host == L.ST_TOO_LARGE).any()):
         forget_shape(*shape)
-    _raise_for_status(host, what)
+    _raise_for_status(host, what, sparse="sparse cones" in what)
 
 
 def flush_checks() -> None:
@@ -135,8 +136,8 @@ class _ConeLossFunction(torch.autograd.Function):
         if lazy:
             _poll_checks()  # the verdicts of earlier calls that have arrived
             kwargs = dict(kwargs, check=False)
-        if warm is not None and mode not in _WARM_MODES:
-            warm = None
+        if warm is not None and (mode not in _WARM_MODES or isinstance(tight_ctrs, SparseCones)):
+            warm = None  # (a batch on the sparse wire format runs cold)
         if warm is not None and not isinstance(tight_ctrs, (PackedBatch, PreparedCones)) and _warm_dense_ok(tight_ctrs, kwargs) \
                 and tight_ctrs.device == warm.device:
             # warm start on a plain dense batch: the split form of the fused step (pack-only launch, then solve)
@@ -155,6 +156,8 @@ class _ConeLossFunction(torch.autograd.Function):
                 from . import qpsolver
 
                 qpsolver._settled.add(tight_ctrs.shape[1:])  # a clean strict call: later lazy calls may run unchecked
+        elif isinstance(tight_ctrs, SparseCones):  # sparse wire format (cave_amd/sparse.py): no dense tensor anywhere
+            o = cone_op_sparse(tight_ctrs, pred_cost, mode, sign, inner_ratio, outputs=("loss", "grad"), **_packed_kwargs(kwargs))
         else:
             if lazy and not _dense_shape_settled(tight_ctrs):
                 kwargs = dict(kwargs, check=True)  # first call for this shape: strict, so the launch tier can settle
@@ -164,8 +167,11 @@ class _ConeLossFunction(torch.autograd.Function):
             warm.last_iters, warm.last_status, warm.last_hit = o["iters"], o["status"], o.get("warm_hit")
         loss, grad = o["loss"], o["grad"]
         if lazy:
-            shape = None if isinstance(tight_ctrs, PackedBatch) else (int(tight_ctrs.shape[1]), int(tight_ctrs.shape[2]))
-            _defer_check(o["status"], "solver='hip' (lazy check)", shape)
+            if isinstance(tight_ctrs, SparseCones):
+                _defer_check(o["status"], "solver='hip' (lazy check, sparse cones)", (tight_ctrs.m_max, tight_ctrs.d))
+            else:
+                shape = None if isinstance(tight_ctrs, PackedBatch) else (int(tight_ctrs.shape[1]), int(tight_ctrs.shape[2]))
+                _defer_check(o["status"], "solver='hip' (lazy check)", shape)
             # the verdict arrives a call or two late: until then a failed instance (NaN-filled outputs) must not reach
             # the optimizer.  The step kernel zeroes its loss and gradient itself (CAVE_STEP_ZERO_FAILED); after the
             # other kernels it is masked here, on the device (no host sync either way)
@@ -195,6 +201,9 @@ class abstractConeAlignedCosine(optModule):
         raise NotImplementedError
 
     def forward(self, pred_cost: torch.Tensor, tight_ctrs: torch.Tensor) -> torch.Tensor:
+        """`tight_ctrs`: the reference's dense (B, m_max, d) tensor, a PackedBatch (store + ids), a PreparedCones, or a
+        cave_amd.sparse.SparseCones (the sparse wire format: same loss and gradient as the dense tensor it stands for;
+        ``check`` as for a PackedBatch; ``solver_kwargs["warm_start"]`` does not apply to it -- such a batch runs cold)."""
         sign = sense_sign(self.optmodel.modelSense)  # ValueError on a bad sense, src/cave.py:62-67
         kwargs = self._solver_kwargs_for_call()
         mode = self._mode()
@@ -207,7 +216,7 @@ class abstractConeAlignedCosine(optModule):
         """The module's multiplier cache (solver_kwargs={"warm_start": ...}) when this call can use it -- a projection
         mode on a prepared batch or a plain dense batch the fused step takes; None otherwise (a PackedBatch warm-starts
         through its store).  Created on the device of the first call that can use it."""
-        if mode not in _WARM_MODES or isinstance(tight_ctrs, PackedBatch):
+        if mode not in _WARM_MODES or isinstance(tight_ctrs, (PackedBatch, SparseCones)):
             return None
         if not isinstance(tight_ctrs, PreparedCones) and not (isinstance(tight_ctrs, torch.Tensor) and
                                                               _warm_dense_ok(tight_ctrs, _op_kwargs(kwargs))):
@@ -252,6 +261,9 @@ class abstractConeAlignedCosine(optModule):
             if isinstance(tight_ctrs, PackedBatch):
                 o = tight_ctrs.store.cone_op(tight_ctrs.ids, signed_cost, self._mode(), 1.0, self._inner_ratio(),
                                              outputs=("target",), **_packed_kwargs(self._solver_kwargs_for_call()))
+            elif isinstance(tight_ctrs, SparseCones):
+                o = cone_op_sparse(tight_ctrs, signed_cost, self._mode(), 1.0, self._inner_ratio(),
+                                   outputs=("target",), **_packed_kwargs(self._solver_kwargs_for_call()))
             else:
                 o = cone_op_dense(tight_ctrs, signed_cost, self._mode(), 1.0, self._inner_ratio(),
                                   outputs=("target",), **_op_kwargs(self._solver_kwargs_for_call()))

@@ -286,6 +286,91 @@ int32_t cave_hip_cone_packed_large(const cave_cone_store* store, const int64_t* 
   return CAVE_OK;
 }
 
+// ------------------------------------------------------------------ sparse wire format
+
+static int32_t check_sparse(const char* who, const cave_sparse_cones* s) {
+  if (!s || s->B < 0 || s->m_max < 0 || s->m_max > 65535 || s->d <= 0 || s->d > 65535) {
+    snprintf(g_err, sizeof(g_err), "%s: bad batch (need 0 <= m_max <= 65535, 0 < d <= 65535)", who);
+    return CAVE_E_INVALID;
+  }
+  if (s->B > 0 && (!s->ent_off || !s->key || !s->val || (((uintptr_t)s->key | (uintptr_t)s->val) & 3u) ||
+                   ((uintptr_t)s->ent_off & 7u))) {
+    snprintf(g_err, sizeof(g_err), "%s: null or misaligned ent_off / key / val", who);
+    return CAVE_E_INVALID;
+  }
+  return CAVE_OK;
+}
+
+static SparsePackParams sparse_params(const cave_sparse_cones* s, int64_t nnz_cap, int32_t lds_bytes) {
+  SparsePackParams P;
+  memset(&P, 0, sizeof(P));
+  P.ent_off = s->ent_off; P.key = s->key; P.val = s->val; P.B = s->B; P.m = s->m_max; P.d = s->d;
+  P.nnz_cap = (uint32_t)nnz_cap; P.lds_bytes = (uint32_t)lds_bytes;
+  return P;
+}
+
+#define CAVE_LAUNCH_SPARSE(WAVES, B, LDS, STREAM, PARAMS, WHAT)                                                \
+  do {                                                                                                         \
+    if ((B) >= (int64_t)1 << 31) return fail(CAVE_E_INVALID, WHAT ": batch too large (B < 2^31)");              \
+    const unsigned grid_ = (unsigned)(B);                                                                      \
+    hipError_t e_;                                                                                             \
+    if ((WAVES) == 8) e_ = launch_pack_sparse_w8(grid_, (uint32_t)(LDS), (hipStream_t)(STREAM), PARAMS);       \
+    else if ((WAVES) == 2) e_ = launch_pack_sparse_w2(grid_, (uint32_t)(LDS), (hipStream_t)(STREAM), PARAMS);  \
+    else e_ = launch_pack_sparse_w4(grid_, (uint32_t)(LDS), (hipStream_t)(STREAM), PARAMS);                    \
+    if (e_ != hipSuccess) return fail(CAVE_E_LAUNCH, "launch " WHAT, e_);                                      \
+  } while (0)
+
+int32_t cave_hip_pack_count_sparse(const cave_sparse_cones* cones, int32_t nnz_cap, int32_t lds_bytes, int32_t waves,
+                                   int32_t* n_rows, int32_t* n_nnz, int32_t* status, void* stream) {
+  int32_t rc = check_sparse("pack_count_sparse", cones);
+  if (rc != CAVE_OK) return rc;
+  if (cones->B == 0) return CAVE_OK;
+  if (!n_rows || !n_nnz) return fail(CAVE_E_INVALID, "pack_count_sparse: null pointer");
+  if (!resolve_limits(cones->m_max, cones->d, nnz_cap, lds_bytes, false)) return fail(CAVE_E_INVALID, "pack_count_sparse: bad limits");
+  if (!waves_ok(waves) || waves == 1) return fail(CAVE_E_INVALID, "pack_count_sparse: waves must be 0, 2, 4 or 8");
+  SparsePackParams P = sparse_params(cones, nnz_cap, lds_bytes);
+  P.n_rows = n_rows; P.n_nnz = n_nnz; P.status = status; P.fill = 0;
+  CAVE_LAUNCH_SPARSE(waves, cones->B, lds_bytes, stream, P, "cone_pack_sparse_kernel(count)");
+  return CAVE_OK;
+}
+
+int32_t cave_hip_pack_fill_sparse(const cave_sparse_cones* cones, int32_t nnz_cap, int32_t lds_bytes, int32_t waves,
+                                  const cave_cone_store* store, int64_t slot0, int32_t* status, void* stream) {
+  int32_t rc = check_sparse("pack_fill_sparse", cones);
+  if (rc != CAVE_OK) return rc;
+  if (cones->B == 0) return CAVE_OK;
+  if (!store) return fail(CAVE_E_INVALID, "pack_fill_sparse: null pointer");
+  if (store->d != cones->d || slot0 < 0 || slot0 + cones->B > store->n) return fail(CAVE_E_INVALID, "pack_fill_sparse: store mismatch");
+  if (!resolve_limits(cones->m_max, cones->d, nnz_cap, lds_bytes, false)) return fail(CAVE_E_INVALID, "pack_fill_sparse: bad limits");
+  if (!waves_ok(waves) || waves == 1) return fail(CAVE_E_INVALID, "pack_fill_sparse: waves must be 0, 2, 4 or 8");
+  if ((store->n_rows == nullptr) != (store->n_nnz == nullptr)) return fail(CAVE_E_INVALID, "pack_fill_sparse: n_rows and n_nnz go together");
+  SparsePackParams P = sparse_params(cones, nnz_cap, lds_bytes);
+  P.status = status; P.store = *store; P.slot0 = slot0; P.fill = 1;
+  CAVE_LAUNCH_SPARSE(waves, cones->B, lds_bytes, stream, P, "cone_pack_sparse_kernel(fill)");
+  return CAVE_OK;
+}
+
+int32_t cave_hip_pack_large_sparse(const cave_sparse_cones* cones, int64_t nnz_cap, void* workspace, int64_t slice_bytes,
+                                   int32_t n_slots, int32_t* n_rows, int32_t* n_nnz, const cave_cone_store* store,
+                                   int64_t slot0, int32_t* status, void* stream) {
+  int32_t rc = check_sparse("pack_large_sparse", cones);
+  if (rc != CAVE_OK) return rc;
+  const int64_t B = cones->B;
+  if (B == 0) return CAVE_OK;
+  if (!store && (!n_rows || !n_nnz)) return fail(CAVE_E_INVALID, "pack_large_sparse: count pass needs n_rows and n_nnz");
+  if (store && (store->d != cones->d || slot0 < 0 || slot0 + B > store->n)) return fail(CAVE_E_INVALID, "pack_large_sparse: store mismatch");
+  if (nnz_cap <= 0 || nnz_cap >= (int64_t)1 << 31) return fail(CAVE_E_INVALID, "pack_large_sparse: bad nnz_cap");
+  int32_t lds = 1024;
+  rc = check_large("pack_large_sparse", workspace, slice_bytes, n_slots, lds);
+  if (rc != CAVE_OK) return rc;
+  SparsePackParams P = sparse_params(cones, nnz_cap, lds);
+  P.n_rows = n_rows; P.n_nnz = n_nnz; P.status = status;
+  if (store) { P.store = *store; P.slot0 = slot0; P.fill = 1; }
+  LargeWs W{(unsigned char*)workspace, (uint64_t)slice_bytes};
+  CAVE_LAUNCH_LARGE(launch_pack_sparse_large, B, n_slots, lds, stream, P, W, "cone_pack_sparse_large_kernel");
+  return CAVE_OK;
+}
+
 // ------------------------------------------------------------------ fused step
 
 static int32_t step_limits(int64_t m_max, int64_t d, int32_t& cap, int32_t& lds) {

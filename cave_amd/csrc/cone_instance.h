@@ -45,6 +45,23 @@ struct PackParams {
   int32_t fill;
 };
 
+// the same pass from the sparse wire format (include/cave_hip.h cave_sparse_cones): a kernel argument of its own, so
+// that the dense pack kernels keep theirs
+struct SparsePackParams {
+  const int64_t* ent_off;
+  const uint32_t* key;
+  const float* val;
+  int64_t B;
+  int32_t m, d;
+  uint32_t nnz_cap, lds_bytes;
+  int32_t* n_rows;
+  int32_t* n_nnz;
+  int32_t* status;
+  cave_cone_store store;  // fill pass only
+  int64_t slot0;
+  int32_t fill;
+};
+
 struct PackedParams {
   cave_cone_store store;
   const int64_t* ids;
@@ -115,6 +132,90 @@ CAVE_HD int32_t scan_and_build(C& c, Arena& ar, ConeBuild& cb, const float* A, i
   }
   c.sync();
   cb.nnz_all = nnz;
+  return build_cone(c, ar, cb);
+}
+
+// 16-byte groups of the sparse wire format (plain vector types: the serial and SIMT test builds have no float4)
+typedef uint32_t sparse_u32x4 __attribute__((vector_size(16), may_alias));
+typedef float sparse_f32x4 __attribute__((vector_size(16), may_alias));
+#if defined(__HIPCC__) && !defined(CAVE_SIMT_EMUL) && !defined(CAVE_NO_NT_LOADS)
+#define CAVE_NT_LOAD_V4(p) __builtin_nontemporal_load(p)
+#else
+#define CAVE_NT_LOAD_V4(p) (*(p))
+#endif
+
+// The second producer of build_cone's input: one instance of the sparse wire format (include/cave_hip.h
+// cave_sparse_cones) -- `n` entries, key = (row << 16) | col strictly increasing (= row-major order), val non-zero and
+// finite.  That is what scan_and_build leaves in cb.erc / cb.eall, so the loader is one coalesced copy (16-byte
+// non-temporal loads: the input is read once) with the per-row counts and the validation in the same pass.  Same
+// reservations from the top of the arena as the dense form (dump slots included: the same instance then fits, or
+// does not fit, the same launch limits on both routes).  An entry that breaks the contract is not stored and not
+// counted; the instance reports ST_BAD_INPUT.  Each entry's predecessor is read from memory (same or previous cache
+// line), so no lane waits for another.
+template <class C, bool LARGE = false>
+CAVE_HD int32_t load_sparse_and_build(C& c, Arena& ar, ConeBuild& cb, const uint32_t* key, const float* val, int64_t nent,
+                                      int m, int d, uint32_t cap) {
+  constexpr uint32_t NT = (uint32_t)C::NT;
+  cb.d = d;
+  cb.m = m;
+  if (m > 0xffff || d > 0xffff) return ST_TOO_LARGE;
+  const uint32_t dump_slots = LARGE ? 0u : NT;
+  cb.erc = ar.get_top<uint32_t>(cap + dump_slots);
+  cb.eall = ar.get_top<float>(cap + dump_slots);
+  cb.rptr = ar.get_top<uint32_t>((uint32_t)m + 1u);
+  if (ar.ovf) return ST_TOO_LARGE;
+  for (int r = c.tid(); r <= m; r += C::NT) cb.rptr[r] = 0u;
+  c.sync();
+  CAVE_T0();
+  if (nent < 0) return ST_BAD_INPUT;
+  if (nent > (int64_t)cap) return ST_TOO_LARGE;
+  const uint32_t n = (uint32_t)nent, tid = (uint32_t)c.tid();
+  uint32_t bad = 0;
+  // entry e with key k, value v; prev = key of entry e - 1 (ignored for e = 0)
+  auto take = [&](uint32_t e, uint32_t k, uint32_t prev, float v) {
+    const uint32_t row = k >> 16, col = k & 0xffffu;
+    const bool ok = (e == 0u || k > prev) && row < (uint32_t)m && col < (uint32_t)d && v != 0.0f &&
+                    (f2u(v) & 0x7f800000u) != 0x7f800000u;
+    if (ok) {
+      cb.erc[e] = k;
+      cb.eall[e] = v;
+      c.atomic_add_u32(&cb.rptr[row], 1u);
+    } else bad = 1u;
+  };
+  // [0, head): up to the first 16-byte boundary of the two arrays (they share the offset; bases that are not
+  // congruent modulo 16 take the single-entry form throughout)
+  uint32_t head = n;
+  if ((((uintptr_t)key ^ (uintptr_t)val) & 15u) == 0u) {
+    head = (uint32_t)(((16u - (uint32_t)((uintptr_t)key & 15u)) & 15u) >> 2);
+    if (head > n) head = n;
+  }
+  for (uint32_t e = tid; e < head; e += NT) take(e, key[e], e ? key[e - 1u] : 0u, val[e]);
+  const uint32_t n4 = (n - head) >> 2;
+  const sparse_u32x4* K4 = reinterpret_cast<const sparse_u32x4*>(key + head);
+  const sparse_f32x4* V4 = reinterpret_cast<const sparse_f32x4*>(val + head);
+  for (uint32_t i0 = tid; i0 < n4; i0 += 2u * NT) {  // two groups per thread in flight; clamped, unconditional loads
+    const uint32_t i1 = i0 + NT, j1 = i1 < n4 ? i1 : n4 - 1u;
+    const uint32_t e0 = head + 4u * i0, e1 = head + 4u * j1;
+    const sparse_u32x4 ka = CAVE_NT_LOAD_V4(&K4[i0]), kb = CAVE_NT_LOAD_V4(&K4[j1]);
+    const sparse_f32x4 va = CAVE_NT_LOAD_V4(&V4[i0]), vb = CAVE_NT_LOAD_V4(&V4[j1]);
+    const uint32_t pa = e0 ? key[e0 - 1u] : 0u, pb = e1 ? key[e1 - 1u] : 0u;
+    take(e0, ka[0], pa, va[0]);
+    take(e0 + 1u, ka[1], ka[0], va[1]);
+    take(e0 + 2u, ka[2], ka[1], va[2]);
+    take(e0 + 3u, ka[3], ka[2], va[3]);
+    if (i1 < n4) {
+      take(e1, kb[0], pb, vb[0]);
+      take(e1 + 1u, kb[1], kb[0], vb[1]);
+      take(e1 + 2u, kb[2], kb[1], vb[2]);
+      take(e1 + 3u, kb[3], kb[2], vb[3]);
+    }
+  }
+  for (uint32_t e = head + 4u * n4 + tid; e < n; e += NT) take(e, key[e], e ? key[e - 1u] : 0u, val[e]);
+  c.sync();
+  CAVE_ACC(10);
+  bad = c.reduce_add_u32(bad);
+  if (bad != 0u) return ST_BAD_INPUT;
+  cb.nnz_all = n;
   return build_cone(c, ar, cb);
 }
 
@@ -563,6 +664,79 @@ CAVE_HD void run_pack_instance(C& c, unsigned char* smem, const PackParams& P, i
   ConeBuild cb;
   CAVE_T0();
   int32_t st = scan_and_build<C, LARGE>(c, ar, cb, P.ctrs + b * (int64_t)m * d, m, d, P.nnz_cap);
+  CAVE_ACC(0);
+  if (!P.fill) {
+    if (c.tid() == 0) {
+      P.n_rows[b] = (st == ST_OK) ? cb.p : 0;
+      P.n_nnz[b] = (st == ST_OK) ? (int32_t)cb.nnzM : 0;
+      if (P.status) P.status[b] = st;
+    }
+    return;
+  }
+  const cave_cone_store& S = P.store;
+  const int64_t slot = P.slot0 + b;
+  float* avg = (st == ST_OK) ? ar.get<float>(d) : nullptr;
+  if (st == ST_OK && ar.ovf) st = ST_TOO_LARGE;
+  if (st == ST_OK) {
+    const int64_t r0 = S.row_off[slot], z0 = S.nnz_off[slot];
+    const bool slots = S.n_rows != nullptr;  // slot mode: the offsets are capacity windows
+    // exact-fit store: it was sized from pass 1, refuse to write past it; slot mode: the instance must fit its window
+    if (!slots && ((int64_t)cb.p != S.row_off[slot + 1] - r0 || (int64_t)cb.nnzM != S.nnz_off[slot + 1] - z0)) st = ST_BAD_INPUT;
+    else if (slots && ((int64_t)cb.p > S.row_off[slot + 1] - r0 || (int64_t)cb.nnzM > S.nnz_off[slot + 1] - z0)) st = ST_TOO_LARGE;
+    else {
+      compute_avg(c, cb, avg);
+      for (int k = c.tid(); k < d; k += NT) {
+        S.usign[slot * d + k] = cb.usign[k];
+        S.avg[slot * d + k] = avg[k];
+      }
+      for (int k = c.tid(); k <= d; k += NT) S.cptr[slot * (d + 1) + k] = cb.cptr[k];
+      // reduced rows: extents, kinds, CSR entries (values expanded from the sign bit in +-1 mode)
+      for (int i = c.tid(); i < cb.p; i += NT) {
+        S.rlo[r0 + i] = cb.mptr[i];
+        S.rhi[r0 + i] = cb.mptr[i + 1];
+        S.vkind[r0 + i] = cb.vkind[i];
+      }
+      for (uint32_t e = c.tid(); e < cb.nnzM; e += NT) {
+        const uint32_t x = cb.mcol[e];
+        S.ccol[z0 + e] = (uint16_t)(cb.pm1 ? (x & 0x7fffu) : x);
+        S.cval[z0 + e] = cb.pm1 ? ((x & 0x8000u) ? -1.0f : 1.0f) : cb.mval[e];
+      }
+      for (uint32_t e = c.tid(); e < cb.nnzM; e += NT) {
+        const uint32_t x = cb.cvar[e];
+        S.cvar[z0 + e] = (uint16_t)(cb.pm1 ? (x & 0x7fffu) : x);
+        S.cvalc[z0 + e] = cb.pm1 ? ((x & 0x8000u) ? -1.0f : 1.0f) : cb.cvalc[e];
+      }
+      if (c.tid() == 0) {
+        S.n_valid[slot] = cb.n_valid_proj;
+        S.flags[slot] = (uint8_t)(cb.pm1 ? 1 : 0);
+      }
+    }
+  }
+  CAVE_ACC(1);
+  if (S.n_rows != nullptr && c.tid() == 0) {
+    S.n_rows[slot] = st == ST_OK ? cb.p : -1;  // -1: this slot holds no cone (the packed operator reports TOO_LARGE)
+    S.n_nnz[slot] = st == ST_OK ? (int32_t)cb.nnzM : 0;
+  }
+  if (c.tid() == 0 && P.status) P.status[b] = st;
+}
+
+// Twin of run_pack_instance for one instance of the sparse wire format: the producer differs (load_sparse_and_build
+// instead of scan_and_build), everything after it is the same text.  A twin and not a shared tail: the dense pack
+// kernels keep their code objects instruction for instruction that way (a shared tail function changed their
+// register allocation).  A change to one of the two belongs in the other; tests/test_sparse_cpu.py and
+// tests/test_gpu_sparse.py compare the stores they write bit for bit.
+template <class C, bool LARGE = false>
+CAVE_HD void run_pack_sparse_instance(C& c, unsigned char* smem, const SparsePackParams& P, int64_t b,
+                                      unsigned char* ws = nullptr, uint32_t ws_bytes = 0) {
+  const int d = P.d, m = P.m;
+  const int NT = C::NT;
+  Arena ar;
+  if constexpr (LARGE) ar.init(ws, ws_bytes);
+  else ar.init(smem + C::SCRATCH_BYTES, P.lds_bytes - C::SCRATCH_BYTES);
+  ConeBuild cb;
+  CAVE_T0();
+  const int64_t e0 = P.ent_off[b];
+  int32_t st = load_sparse_and_build<C, LARGE>(c, ar, cb, P.key + e0, P.val + e0, P.ent_off[b + 1] - e0, m, d, P.nnz_cap);
   CAVE_ACC(0);
   if (!P.fill) {
     if (c.tid() == 0) {

@@ -133,6 +133,35 @@ __global__ __launch_bounds__(C::NT, 2) void cone_pack_large_kernel(PackParams P,
   }
 }
 
+// ---- pack pass from the sparse wire format (cone_instance.h load_sparse_and_build): the shapes of the dense pack
+// kernels, with the coordinate list of an instance copied instead of its dense block scanned
+template <class C>
+__global__ CAVE_BOUNDS(C) void cone_pack_sparse_kernel(SparsePackParams P) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  C c;
+  c.init(smem);
+  const int64_t b = blockIdx.x;
+#ifdef CAVE_STAMPS
+  for (int i = 0; i < 32; ++i) c.st[i] = 0;
+#endif
+  if (b < P.B) run_pack_sparse_instance(c, smem, P, b);
+}
+
+template <class C>
+__global__ __launch_bounds__(C::NT, 2) void cone_pack_sparse_large_kernel(SparsePackParams P, LargeWs W) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  C c;
+  c.init(smem);
+#ifdef CAVE_STAMPS
+  for (int i = 0; i < 32; ++i) c.st[i] = 0;
+#endif
+  unsigned char* ws = W.base + (uint64_t)blockIdx.x * W.slice;
+  for (int64_t b = blockIdx.x; b < P.B; b += gridDim.x) {
+    run_pack_sparse_instance<C, true>(c, smem, P, b, ws, (uint32_t)W.slice);
+    __syncthreads();
+  }
+}
+
 // (MINB = waves per SIMD the register budget is set for: 2 -> 256 VGPRs.  C = CtxL: 4 waves, two workgroups per CU;
 //  CtxL2 / Ctx1: 2 / 1 waves, four and more workgroups per CU where the LDS allows -- for batches that fill the
 //  chip several times over with narrow-band cones, whose elimination runs on one wave anyway: cone_band.h)
@@ -302,6 +331,10 @@ CAVE_DECL_LAUNCH_LARGE(launch_pack_large, PackParams);
 CAVE_DECL_LAUNCH_LARGE(launch_packed_large_w1, PackedParams);
 CAVE_DECL_LAUNCH_LARGE(launch_packed_large_w2, PackedParams);
 CAVE_DECL_LAUNCH_LARGE(launch_packed_large_w4, PackedParams);
+CAVE_DECL_LAUNCH(launch_pack_sparse_w2, SparsePackParams);
+CAVE_DECL_LAUNCH(launch_pack_sparse_w4, SparsePackParams);
+CAVE_DECL_LAUNCH(launch_pack_sparse_w8, SparsePackParams);
+CAVE_DECL_LAUNCH_LARGE(launch_pack_sparse_large, SparsePackParams);
 CAVE_DECL_LAUNCH(launch_step, StepParams);
 CAVE_DECL_LAUNCH(launch_step_warm, StepParamsWarm);
 CAVE_DECL_LAUNCH(launch_lite_from_packed, LiteFromPackedParams);

@@ -10,6 +10,7 @@ remaining rows -> CSR + CSC, plus the precomputed `_average_ctrs` vector) and a
 batch is just a tensor of instance ids.
 
     store = ConeStore.from_ragged(dataset.ctrs)         # one-time, streams the dense form through the GPU
+    store = ConeStore.from_sparse(SparseCones.from_ragged(dataset.ctrs))   # the same store, no dense form anywhere
     ids   = torch.tensor([...])                         # what the collate_fn replacement returns
     out   = store.cone_op(ids, pred_cost, mode, sign)   # same fused kernel as the dense path
 """
@@ -22,8 +23,9 @@ import torch
 
 from . import _lib
 from .qpsolver import _grow_limits, _large_guess, _raise_for_status, fast_path_cannot_fit
+from .sparse import collate_sparse
 
-__all__ = ["ConeStore", "PackedBatch", "collate_ids", "prefetch"]
+__all__ = ["ConeStore", "PackedBatch", "collate_ids", "collate_sparse", "prefetch"]
 
 
 class ConeStore:
@@ -37,6 +39,7 @@ class ConeStore:
         self.max_rows = 0
         self.max_nnz = 0
         self._c = None
+        self.bad_input = None  # from_sparse(strict=False): instances the device rejected
 
     # ------------------------------------------------------------------ build
     @classmethod
@@ -148,6 +151,26 @@ class ConeStore:
         if d is None:
             raise ValueError("ConeStore: no chunks")
         self = cls(d, dev)
+        self._allocate(counts)
+        # pass 2: fill
+        slot = 0
+        for ch, lim in zip(chunks, limits):
+            x = ch.to(device=dev, dtype=torch.float32).contiguous()
+            B, m, _ = x.shape
+            status = torch.empty(B, dtype=torch.int32, device=dev)
+            if lim[0] == "large":
+                pack_large(x, lim[1], None, None, C.byref(self._c), slot, status)
+            else:
+                _lib.check(lib.cave_hip_pack_fill(_lib.ptr(x), B, m, d, lim[0], lim[1], lim[2], C.byref(self._c), slot,
+                                                  _lib.ptr(status), stream), "cave_hip_pack_fill")
+            _raise_for_status(status, "ConeStore fill")
+            slot += B
+        self._finish_build()
+        return self
+
+    def _allocate(self, counts) -> None:
+        """Size the exact-fit store from the count pass (`counts`: per chunk, (n_rows, n_nnz) device tensors)."""
+        dev, d = self.device, self.d
         n_rows = torch.cat([c[0] for c in counts]).to(torch.int64)
         n_nnz = torch.cat([c[1] for c in counts]).to(torch.int64)
         N = int(n_rows.numel())
@@ -173,19 +196,12 @@ class ConeStore:
         t["cvar"] = torch.zeros(max(Z, 1), dtype=torch.int16, device=dev)
         t["cvalc"] = torch.zeros(max(Z, 1), dtype=torch.float32, device=dev)
         self._c = _lib.Store(n=N, d=d, reserved=0, **{k: v.data_ptr() for k, v in t.items()})
-        # pass 2: fill
-        slot = 0
-        for ch, lim in zip(chunks, limits):
-            x = ch.to(device=dev, dtype=torch.float32).contiguous()
-            B, m, _ = x.shape
-            status = torch.empty(B, dtype=torch.int32, device=dev)
-            if lim[0] == "large":
-                pack_large(x, lim[1], None, None, C.byref(self._c), slot, status)
-            else:
-                _lib.check(lib.cave_hip_pack_fill(_lib.ptr(x), B, m, d, lim[0], lim[1], lim[2], C.byref(self._c), slot,
-                                                  _lib.ptr(status), stream), "cave_hip_pack_fill")
-            _raise_for_status(status, "ConeStore fill")
-            slot += B
+
+    def _finish_build(self) -> None:
+        """What follows the fill pass, whichever wire format it read: launch figures of the store, sign folding,
+        band figures and red-black cache of the large path, lite slots."""
+        lib = _lib.load()
+        dev, d, t, N = self.device, self.d, self.t, self.n
         self.warm_start = False
         self.diet_min_batch = 256  # batches up to one workgroup per compute unit keep the ordinary (faster) layout
         self.fits4 = self.max_rows <= 32  # 4-wave workgroups hold reduced systems up to 32 rows
@@ -226,6 +242,95 @@ class ConeStore:
                 self.rb_cache = torch.zeros(self.n * stride, dtype=torch.uint8, device=dev)
                 self._c.rb_cache, self._c.rb_stride = self.rb_cache.data_ptr(), stride
         self._build_lite()
+
+    # ------------------------------------------------------- build from the sparse wire format
+    @classmethod
+    def from_sparse(cls, cones, chunk: int = 1024, strict: bool = True) -> "ConeStore":
+        """Pack a cave_amd.sparse.SparseCones (host or device) without a dense tensor at any point: count pass, prefix
+        sums, fill pass, both through the sparse pack kernels (cave_hip_pack_*_sparse), `chunk` instances at a time,
+        on the tier ladder of from_chunks_lazy (default limits; the full arena with waves = 8; the large-cone path).
+        The store holds the bits the dense route writes for `cones.densify()` packed in the same chunks.  The host
+        knows every instance's non-zero count, so the large path needs no retries for its capacity.
+        A malformed instance (the device checks every entry: include/cave_hip.h) raises ValueError; with
+        ``strict=False`` it is left as an empty cone and marked in `store.bad_input` ([n] bool, else None)."""
+        lib = _lib.load()
+        dev = cones.device if cones.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        d, m = cones.d, cones.m_max
+        if len(cones) == 0:
+            raise ValueError("ConeStore: no chunks")
+        chunk = max(1, int(chunk))
+        spans = [(i, min(i + chunk, len(cones))) for i in range(0, len(cones), chunk)]
+        with torch.cuda.device(dev):
+            stream = _lib.current_stream()
+
+            def pack_large(x, cap, n_rows, n_nnz, store, slot, status):
+                slice_bytes = int(lib.cave_hip_large_slice_bytes(m, d, cap, 1))
+                # one workgroup per compute unit: the workspace (1.8 MB per slot at TSP-100) is then the largest transient
+                # of the build, and stays below what the dense route stages for four instances
+                slots = min(_lib.large_slots(dev, len(x), slice_bytes), 256)
+                ws = _lib.workspace(dev, slots * slice_bytes)
+                _lib.check(lib.cave_hip_pack_large_sparse(x.c_ref(), cap, _lib.ptr(ws), slice_bytes, slots, _lib.ptr(n_rows),
+                                                          _lib.ptr(n_nnz), store, slot, _lib.ptr(status), stream),
+                           "cave_hip_pack_large_sparse")
+
+            counts, limits, bad_chunks = [], [], []
+            for lo, hi in spans:
+                x = cones[lo:hi].to(dev)
+                B = hi - lo
+                n_rows = torch.empty(B, dtype=torch.int32, device=dev)
+                n_nnz = torch.empty(B, dtype=torch.int32, device=dev)
+                status = torch.empty(B, dtype=torch.int32, device=dev)
+                lim = (0, 0, 0)
+                tier = 2 if fast_path_cannot_fit(d) else 0
+                while tier < 2:
+                    _lib.check(lib.cave_hip_pack_count_sparse(x.c_ref(), lim[0], lim[1], lim[2], _lib.ptr(n_rows),
+                                                              _lib.ptr(n_nnz), _lib.ptr(status), stream),
+                               "cave_hip_pack_count_sparse")
+                    if not bool((status == _lib.ST_TOO_LARGE).any()):
+                        break
+                    tier += 1
+                    if tier == 1:
+                        cap, lds = _grow_limits(m, d)
+                        lim = (cap, lds, 8)
+                if tier == 2:
+                    cap = max(64, int(x.nnz_per_instance.max()))
+                    pack_large(x, cap, n_rows, n_nnz, None, 0, status)
+                    lim = ("large", cap)
+                if not strict:
+                    bad_chunks.append(status == _lib.ST_BAD_INPUT)
+                    status = torch.where(bad_chunks[-1], torch.zeros_like(status), status)
+                _raise_for_status(status, "ConeStore pack", sparse=True, offset=lo)
+                counts.append((n_rows, n_nnz))
+                limits.append(lim)
+            self = cls(d, dev)
+            self._allocate(counts)
+            for (lo, hi), lim in zip(spans, limits):
+                x = cones[lo:hi].to(dev)
+                status = torch.empty(hi - lo, dtype=torch.int32, device=dev)
+                if lim[0] == "large":
+                    pack_large(x, lim[1], None, None, C.byref(self._c), lo, status)
+                else:
+                    _lib.check(lib.cave_hip_pack_fill_sparse(x.c_ref(), lim[0], lim[1], lim[2], C.byref(self._c), lo,
+                                                             _lib.ptr(status), stream), "cave_hip_pack_fill_sparse")
+                if not strict:
+                    status = torch.where(status == _lib.ST_BAD_INPUT, torch.zeros_like(status), status)
+                _raise_for_status(status, "ConeStore fill", sparse=True, offset=lo)
+            self._finish_build()
+            bad = torch.cat(bad_chunks) if bad_chunks else None
+            self.bad_input = bad if bad is not None and bool(bad.any()) else None
+        return self
+
+    @classmethod
+    def from_sparse_shard(cls, cones, rank: int, world: int, chunk: int = 1024) -> "ConeStore":
+        """As from_ragged_shard, for a SparseCones dataset: the balancing weights are the entry counts of `ent_off`
+        (no pass over dense data), and this rank packs only its own cones."""
+        from .dist import weighted_shards
+
+        weights = [int(w) for w in cones.nnz_per_instance.cpu()]
+        mine = weighted_shards(weights, world)[rank]
+        self = cls.from_sparse(cones[[int(i) for i in mine]], chunk)
+        self.global_ids = torch.as_tensor(mine, dtype=torch.int64)
+        self.shard = (int(rank), int(world))
         return self
 
     def _build_lite(self) -> None:

@@ -23,7 +23,7 @@ from ._lib import (MODE_AVG, MODE_EXACT, MODE_HEURISTIC, MODE_INNER, MODE_PROJEC
                    ST_NOT_CONVERGED, ST_OK, ST_TOO_LARGE)
 
 __all__ = ["project_hip", "average_ctrs_hip", "cone_op_dense", "HipSolverError", "PreparedCones", "prepare_dense",
-           "cone_op_prepared", "step_lds_bytes"]
+           "cone_op_prepared", "step_lds_bytes", "cone_op_sparse", "project_hip_sparse"]
 
 
 class HipSolverError(RuntimeError):
@@ -80,6 +80,7 @@ def forget_shape(m: int, d: int) -> None:
     _wide_ok.pop(key, None)
     _large_hint.pop(key, None)
     _split_ok.pop(key, None)
+    _sparse_split_ok.pop(key, None)
     _step_ok.pop(key, None)
     _settled.discard(key)
 
@@ -109,6 +110,7 @@ def fast_path_cannot_fit(d: int) -> bool:
 SPLIT_MAX_D, SPLIT_ROWS, SPLIT_NNZ = 256, 32, 1536
 _slot_stores: dict = {}
 _split_ok: dict[tuple[int, int], bool] = {}  # (m, d) -> the split form fitted every instance of a checked batch
+_sparse_split_ok: dict[tuple[int, int], bool] = {}  # the same for batches on the sparse wire format (cone_op_sparse)
 
 
 class _SlotStore:
@@ -357,19 +359,25 @@ def cone_op_prepared(prep: PreparedCones, pred_cost: torch.Tensor, mode: int, si
     return out
 
 
-def _raise_for_status(status: torch.Tensor, what: str) -> None:
+def _raise_for_status(status: torch.Tensor, what: str, sparse: bool = False, offset: int = 0) -> None:
+    """`sparse`: the cones came in on the sparse wire format, whose loader reports a broken entry as ST_BAD_INPUT.
+    `offset`: batch index of status[0] (a chunk of a larger batch)."""
     st = status.cpu()
     if bool((st == ST_OK).all()):
         return
     bad = int((st != ST_OK).sum())
     first = int((st != ST_OK).nonzero()[0])
     code = int(st[first])
+    first += int(offset)
     if code == ST_NOT_CONVERGED:
         raise HipSolverError(f"{what}: Maximum number of iterations reached ({bad} instance(s), first index {first}).")
     if code == ST_TOO_LARGE:
         raise HipSolverError(
             f"{what}: {bad} cone(s) (first index {first}) did not fit the workspace of the large-cone path "
             "after four 4x size increases (non-zeros / band of the reduced system).")
+    if code == ST_BAD_INPUT and sparse:
+        raise ValueError(f"{what}: malformed sparse cone: unsorted / out-of-range / zero or non-finite entry (or "
+                         f"non-finite input) in {bad} instance(s), first index {first}.")
     if code == ST_BAD_INPUT:
         raise ValueError(f"{what}: non-finite input in {bad} instance(s), first index {first}.")
     raise HipSolverError(f"{what}: unknown status {code}")
@@ -522,6 +530,92 @@ def project_hip(tight_ctrs: torch.Tensor, signed_cost: torch.Tensor, max_iter: i
     """
     o = cone_op_dense(tight_ctrs, signed_cost, MODE_PROJECT, 1.0, 0.0, max_iter=max_iter, nnz_cap=nnz_cap,
                       lds_bytes=lds_bytes, waves=waves, check=check, outputs=("proj", "rnorm"))
+    device, dtype = signed_cost.device, signed_cost.dtype
+    return o["proj"].to(device=device, dtype=dtype), o["rnorm"].to(device=device, dtype=dtype)
+
+
+def cone_op_sparse(cones, pred_cost: torch.Tensor | None, mode: int, sign: float = 1.0, inner_ratio: float = 0.2, *,
+                   max_iter: int = 0, check: bool = True, outputs: tuple[str, ...] = ("proj", "rnorm")) -> dict[str, torch.Tensor]:
+    """cone_op_dense for a batch on the sparse wire format (cave_amd.sparse.SparseCones): no dense tensor anywhere.
+
+    Shapes the split form takes (d <= SPLIT_MAX_D, B <= 2048): cave_hip_pack_fill_sparse in slot mode, four waves per
+    instance, in place of the dense pack launch -- it copies 8 bytes per non-zero instead of streaming the zeros --
+    followed by the same one-wave cave_hip_cone_packed as the dense split form, so the outputs are the dense call's
+    bit for bit.  Anything else, and a split batch that reports CAVE_ST_TOO_LARGE under ``check=True``, builds a
+    transient ConeStore.from_sparse and runs its cone_op on every slot.
+
+    A malformed instance (unsorted or repeated key, row / column out of range, zero or non-finite value) is rejected
+    on the device: ``check=True`` raises ValueError naming the first one; ``check=False`` leaves status
+    CAVE_ST_BAD_INPUT and NaN outputs at its index and the other instances correct."""
+    from .sparse import SparseCones
+
+    lib = _lib.load()
+    if not isinstance(cones, SparseCones):
+        raise TypeError("cone_op_sparse: cones must be a SparseCones")
+    B, m, d = len(cones), cones.m_max, cones.d
+    dev = cones.device if cones.is_cuda else (
+        pred_cost.device if pred_cost is not None and pred_cost.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    x = cones.to(dev)
+    pred = None
+    if pred_cost is not None:
+        if pred_cost.shape != (B, d):
+            raise ValueError(f"pred_cost must have shape ({B}, {d}), got {tuple(pred_cost.shape)}")
+        pred = _as_device(pred_cost, dev)
+    elif mode != MODE_AVG:
+        raise ValueError("pred_cost is required")
+    what = "solver='hip' (sparse cones)"
+    with torch.cuda.device(dev):
+        if B == 0:
+            out = {name: torch.empty((0,) if name in ("rnorm", "loss") else (0, d), dtype=torch.float32, device=dev)
+                   for name in outputs}
+            out["status"] = out["iters"] = torch.empty(0, dtype=torch.int32, device=dev)
+            return out
+        if 0 < m and d <= SPLIT_MAX_D and B <= 2048 and _sparse_split_ok.get((m, d)) is not False:
+            out: dict[str, torch.Tensor] = {}
+            for name in outputs:
+                out[name] = torch.empty((B,) if name in ("rnorm", "loss") else (B, d), dtype=torch.float32, device=dev)
+            status = torch.empty(B, dtype=torch.int32, device=dev)
+            iters = torch.empty(B, dtype=torch.int32, device=dev)
+            ss = _slot_store(dev, B, d)
+            if ss.lds_bytes <= 0:
+                raise HipSolverError("split form: no LDS configuration")
+            rc = lib.cave_hip_pack_fill_sparse(x.c_ref(), 0, 0, 4, ss.ref, 0, _lib.ptr(ss.pack_status), _lib.current_stream())
+            _lib.check(rc, "cave_hip_pack_fill_sparse (slot mode)")
+            rc = lib.cave_hip_cone_packed(
+                ss.ref, None, _lib.ptr(pred), B, int(mode), float(sign), float(inner_ratio), int(max_iter), ss.lds_bytes, 1,
+                _lib.ptr(out.get("proj")), _lib.ptr(out.get("rnorm")), _lib.ptr(out.get("target")),
+                _lib.ptr(out.get("loss")), _lib.ptr(out.get("grad")), _lib.ptr(status), _lib.ptr(iters),
+                _lib.current_stream())
+            _lib.check(rc, "cave_hip_cone_packed (slot mode)")
+            # an instance the loader rejected left an empty slot, which the solve reports as TOO_LARGE (NaN outputs):
+            # its own verdict is the loader's
+            status = torch.where(ss.pack_status == ST_BAD_INPUT, ss.pack_status, status)
+            out["status"], out["iters"] = status, iters
+            if not check:
+                return out
+            st = status.cpu()
+            if not bool((st == ST_TOO_LARGE).any()):
+                _sparse_split_ok[(m, d)] = True
+                _raise_for_status(st, what, sparse=True)
+                return out
+            _sparse_split_ok[(m, d)] = False
+        from .dataset import ConeStore
+
+        store = ConeStore.from_sparse(x, strict=check)
+        out = store.cone_op(torch.arange(B, dtype=torch.int64, device=dev), pred, mode, sign, inner_ratio, max_iter=max_iter,
+                            check=check, outputs=outputs)
+        bad = store.bad_input
+        if bad is not None:  # (check=False only: the store holds an empty cone in a rejected instance's slot)
+            out["status"] = torch.where(bad, torch.full_like(out["status"], ST_BAD_INPUT), out["status"])
+            for name in outputs:
+                o = out[name]
+                o.masked_fill_(bad if o.dim() == 1 else bad.unsqueeze(1), float("nan"))
+    return out
+
+
+def project_hip_sparse(cones, signed_cost: torch.Tensor, max_iter: int = 0, check: bool = True) -> tuple[torch.Tensor, torch.Tensor]:
+    """project_hip for a SparseCones batch: (proj, rnorm) on signed_cost's device and dtype."""
+    o = cone_op_sparse(cones, signed_cost, MODE_PROJECT, 1.0, 0.0, max_iter=max_iter, check=check, outputs=("proj", "rnorm"))
     device, dtype = signed_cost.device, signed_cost.dtype
     return o["proj"].to(device=device, dtype=dtype), o["rnorm"].to(device=device, dtype=dtype)
 

@@ -9,6 +9,7 @@ BASELINE configs[0] sizes (5x5 grid, 100 instances, batch 32); `--problem tsp` i
     python examples/train_sp_cave.py --grid 30 30 --num-data 64 --batch 32 --epochs 3 --packed --inner ipm
     python examples/train_sp_cave.py --packed --graph          # the whole step (predictor, loss, backward, Adam) as one HIP graph
     python examples/train_sp_cave.py --problem tsp --prefetch  # dense cones: the next batch's pack rides in this batch's loss call
+    python examples/train_sp_cave.py --sparse [--packed]       # cones on the sparse wire format: no dense padding anywhere
 """
 
 import argparse
@@ -49,13 +50,19 @@ def main(argv=None):
     ap.add_argument("--prefetch", action="store_true",
                     help="(dense cones) wrap the DataLoader in cave_amd.dataset.prefetch: the loop body stays as it is and the "
                          "pack stage of batch i+1 rides in the launch of batch i's loss")
+    ap.add_argument("--sparse", action="store_true",
+                    help="the dataset hands out cones on the sparse wire format (cave_amd.sparse.SparseCones) and the loader "
+                         "collates them with collate_sparse; with --packed the store is built by ConeStore.from_sparse")
     ap.add_argument("--lazy-check", action="store_true", help="solver_kwargs check='lazy': no host sync per step")
     args = ap.parse_args(argv)
     if args.graph and (not args.packed or args.variant == "hybrid"):
         ap.error("--graph needs --packed and a variant without a per-call branch draw")
+    if args.sparse and not args.packed and (args.prefetch or args.warm_start):
+        ap.error("--sparse batches take neither --prefetch nor the dense warm start (they run cold)")
 
     from cave_amd.cave import EPO, exactConeAlignedCosine, innerConeAlignedCosine
-    from cave_amd.dataset import ConeStore, PackedBatch, prefetch
+    from cave_amd.dataset import ConeStore, PackedBatch, collate_sparse, prefetch
+    from cave_amd.sparse import SparseCones
     from cave_amd.tight import (SPConeDataset, TSPConeDataset, sp_gen_data, sp_regret, tsp_gen_data, tsp_regret)
     from torch.nn.utils.rnn import pad_sequence
 
@@ -88,7 +95,12 @@ def main(argv=None):
     else:
         cave = innerConeAlignedCosine(_Model(), solver="hip", solve_ratio=0.3, inner_ratio=0.2, seed=0, solver_kwargs=kw or None)
 
-    store = ConeStore.from_ragged(dataset.ctrs) if args.packed else None
+    # --sparse: what a dataset built from a solver's sparse constraint matrix would keep -- one SparseCones per instance
+    sparse_ctrs = SparseCones.from_ragged(dataset.ctrs) if args.sparse else None
+    if args.packed:
+        store = ConeStore.from_sparse(sparse_ctrs) if args.sparse else ConeStore.from_ragged(dataset.ctrs)
+    else:
+        store = None
     if store is not None and args.warm_start:
         store.enable_warm_start()
 
@@ -97,6 +109,8 @@ def main(argv=None):
         x, c = dataset.feats[idx], dataset.costs[idx]
         if args.packed:
             return x, c, idx
+        if args.sparse:
+            return collate_sparse([(x[j], c[j], sparse_ctrs[i]) for j, i in enumerate(batch)])
         return x, c, pad_sequence([dataset.ctrs[i] for i in batch], batch_first=True, padding_value=0.0)
 
     loader = DataLoader(list(range(len(dataset))), batch_size=args.batch, shuffle=True, collate_fn=collate,

@@ -53,7 +53,7 @@ extern "C" {
 #define CAVE_ST_OK 0
 #define CAVE_ST_NOT_CONVERGED 1 /* iteration cap reached (SciPy raises RuntimeError, src/cave.py:307) */
 #define CAVE_ST_TOO_LARGE 2     /* cone did not fit this launch's LDS arena; retry with larger limits */
-#define CAVE_ST_BAD_INPUT 3     /* non-finite values */
+#define CAVE_ST_BAD_INPUT 3     /* non-finite values; sparse wire format: an entry that breaks its contract */
 
 /* modes */
 #define CAVE_MODE_PROJECT 0
@@ -331,6 +331,38 @@ int32_t cave_hip_cone_step_warm(const cave_lite_store* solve, const int64_t* ids
                                 const float* next_ctrs, int64_t B_next, int64_t m_max, int64_t d, const cave_lite_store* next,
                                 int32_t* pack_status, const cave_warm_cache* warm, const int64_t* keys, uint8_t* warm_hit,
                                 uint32_t* cu_tickets, void* stream);
+
+/* ------------------------------------------------------------------ sparse wire format (additive to v10)
+ * The dense wire format is almost all zeros (TSP-100: 33 447 non-zeros in a 102 MB block).  A batch of cones in
+ * coordinate form, device pointers, caller-owned, read-only:
+ *   ent_off [B+1]  entry offsets of the instances, ent_off[0] = 0, non-decreasing
+ *   key     [Z]    (row << 16) | col, STRICTLY increasing within an instance (= row-major order)
+ *   val     [Z]    non-zero, finite
+ * (key and val 4-byte aligned; 16-byte loads are used when the two bases are congruent modulo 16.)
+ * Checked on the device, per instance, in the pass that reads the entries: a key that is not greater than its
+ * predecessor, a row >= m_max, a column >= d, a zero or a non-finite value give CAVE_ST_BAD_INPUT for that instance
+ * (nothing is read or written out of range); more than nnz_cap entries give CAVE_ST_TOO_LARGE.  An instance without
+ * entries is the empty cone.  m_max, d <= 65535; the dense route's m_max * d < 2^32 does not apply. */
+typedef struct cave_sparse_cones {
+  int64_t B;
+  int32_t m_max, d;
+  const int64_t* ent_off;
+  const uint32_t* key;
+  const float* val;
+} cave_sparse_cones;
+
+/* cave_hip_pack_count / cave_hip_pack_fill / cave_hip_pack_large from the sparse wire format: same arguments with
+ * `ctrs, B, m_max, d` replaced by the batch, same launch limits, same stores (exact-fit and slot mode), and -- the
+ * reduced cone being built by the same code from the same entries -- the same bits in the store as the dense route
+ * writes for the densified batch.  waves: 0 (= 2), 2, 4 or 8; there is no one-wave sparse pack shape (waves = 1:
+ * CAVE_E_INVALID). */
+int32_t cave_hip_pack_count_sparse(const cave_sparse_cones* cones, int32_t nnz_cap, int32_t lds_bytes, int32_t waves,
+                                   int32_t* n_rows, int32_t* n_nnz, int32_t* status, void* stream);
+int32_t cave_hip_pack_fill_sparse(const cave_sparse_cones* cones, int32_t nnz_cap, int32_t lds_bytes, int32_t waves,
+                                  const cave_cone_store* store, int64_t slot0, int32_t* status, void* stream);
+int32_t cave_hip_pack_large_sparse(const cave_sparse_cones* cones, int64_t nnz_cap, void* workspace, int64_t slice_bytes,
+                                   int32_t n_slots, int32_t* n_rows, int32_t* n_nnz, const cave_cone_store* store,
+                                   int64_t slot0, int32_t* status, void* stream);
 
 /* Device-resident stores: cones are static per instance (src/dataset.py:72), so a packed store whose cones qualify
  * builds the lite slots of ALL its instances once (slot i of `dst` from slot i of `src`, dst->n >= src->n) and then

@@ -1,5 +1,5 @@
 """Workload for rocprofv3: BASELINE configs 2 / 3 / 4 at their per-GPU batch on the packed store, every batch slot a
-DISTINCT cone (coordinate-form generator, densified on the GPU a chunk at a time).
+DISTINCT cone (coordinate-form generator, packed from the sparse wire format).
     python tools/diag/large_profile.py tsp50|tsp100|sp30 [B] [steps]"""
 import sys, os, time
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
@@ -7,15 +7,16 @@ import numpy as np, torch
 from cave_amd import synth, _lib
 if os.environ.get("CAVE_SO"): _lib.LIB_PATH = os.path.abspath(os.environ["CAVE_SO"])  # a diagnostic variant of the library
 from cave_amd.dataset import ConeStore
+from cave_amd.sparse import SparseCones
 which = sys.argv[1]
 B = int(sys.argv[2]) if len(sys.argv) > 2 else (1024 if which == "sp30" else 512)
 steps = int(sys.argv[3]) if len(sys.argv) > 3 else 5
 dev = torch.device("cuda")
-kind, size, chunk = {"tsp100": ("tsp", 100, 4), "tsp50": ("tsp", 50, 32), "sp30": ("sp", (30, 30), 32)}[which]
+kind, size = {"tsp100": ("tsp", 100), "tsp50": ("tsp", 50), "sp30": ("sp", (30, 30))}[which]
 MODE = _lib.MODE_EXACT if which == "tsp50" else _lib.MODE_INNER  # (configs[2] is CaVE Exact)
 items, costs, _ = synth.coo_batch(kind, size, B, seed=0)
 d = costs.shape[1]; m_max = max(it[3] for it in items)
-store = ConeStore.from_chunks_lazy(lambda i: synth.densify_on(items[i:i + chunk], d, dev, m_max), list(range(0, B, chunk)))
+store = ConeStore.from_sparse(SparseCones.from_coo(items, d))  # (sparse wire format: no dense staging)
 ids = torch.arange(B, device=dev)
 if os.environ.get("LARGE_WAVES"): store.large_waves = int(os.environ["LARGE_WAVES"])
 torch.manual_seed(0)

@@ -6,11 +6,12 @@ import numpy as np, torch
 from cave_amd import synth, _lib
 if os.environ.get("CAVE_LIB"): _lib.LIB_PATH = os.path.abspath(os.environ["CAVE_LIB"])
 from cave_amd.dataset import ConeStore
+from cave_amd.sparse import SparseCones
 dev = torch.device("cuda"); lib = _lib.load()
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 512
 items, costs, _ = synth.coo_batch("tsp", 50, B, seed=0)
 d = costs.shape[1]; m_max = max(it[3] for it in items)
-store = ConeStore.from_chunks_lazy(lambda i: synth.densify_on(items[i:i + 32], d, dev, m_max), list(range(0, B, 32)))
+store = ConeStore.from_sparse(SparseCones.from_coo(items, d))  # (sparse wire format: no dense staging)
 ids = torch.arange(B, device=dev)
 g = torch.Generator(device="cpu").manual_seed(1)
 pred = torch.tensor(costs, device=dev) + 0.05 * torch.randn(B, d, generator=g).to(dev)
