@@ -79,15 +79,30 @@ _pending_checks: list = []
 LAZY_MAX_PENDING = 4
 
 
-def _examine(host, what, shape) -> None:
+def _examine(host, what, shape, prepared=False) -> None:
     from . import _lib as L
-    from .qpsolver import _raise_for_status, forget_shape
+    from . import qpsolver
+    from .qpsolver import HipSolverError, _raise_for_status, forget_shape
 
     _pinned_free.setdefault(host.numel(), []).append(host)  # pinned allocations are slow: keep them
     if not bool(host.any()):  # every status CAVE_ST_OK (= 0): the common case costs one reduction on the host
         return
-    if shape is not None and bool((host == L.ST_TOO_LARGE).any()):
+    too_large = bool((host == L.ST_TOO_LARGE).any())
+    if shape is not None and too_large:
         forget_shape(*shape)
+        if prepared:
+            # the verdict of a step-kernel launch (a PreparedCones: prepare_dense / prefetch): the batch held a cone the
+            # one-wave solver does not take.  forget_shape alone would leave the shape qualifying, and every later
+            # batch with such a cone would fail the same way: prepare_dense now returns the tensor for this shape and
+            # the next call, status-checked, settles a tier of the general path
+            qpsolver._step_ok[(int(shape[0]), int(shape[1]))] = False
+            bad = int((host == L.ST_TOO_LARGE).sum())
+            first = int((host == L.ST_TOO_LARGE).nonzero()[0])
+            raise HipSolverError(
+                f"{what}: {bad} cone(s) (first index {first}) are not ones the one-wave solver of the fused step takes "
+                "(more than 32 reduced rows, 8 bound rows, 8 entries per column or 1536 non-zeros, entries other than "
+                "+-1, or no room for the active-set scratch); those instances contributed zero loss and zero gradient. "
+                "Later batches of this shape take the general path.")
     _raise_for_status(host, what, sparse="sparse cones" in what)
 
 
@@ -99,29 +114,29 @@ def flush_checks() -> None:
     arena, large-cone path) instead of failing again.  The failed instances of the lazy launch itself
     contributed zero loss and zero gradient (masked on the device), so no NaN reached the optimizer."""
     while _pending_checks:
-        host, event, what, shape = _pending_checks.pop(0)
+        host, event, what, shape, prepared = _pending_checks.pop(0)
         event.synchronize()
-        _examine(host, what, shape)
+        _examine(host, what, shape, prepared)
 
 
 def _poll_checks() -> None:
     """The verdicts that have arrived, without waiting (beyond LAZY_MAX_PENDING outstanding: the oldest is awaited)."""
     while _pending_checks and (_pending_checks[0][1].query() or len(_pending_checks) > LAZY_MAX_PENDING):
-        host, event, what, shape = _pending_checks.pop(0)
+        host, event, what, shape, prepared = _pending_checks.pop(0)
         event.synchronize()
-        _examine(host, what, shape)
+        _examine(host, what, shape, prepared)
 
 
 _pinned_free: dict = {}
 
 
-def _defer_check(status: torch.Tensor, what: str, shape=None) -> None:
+def _defer_check(status: torch.Tensor, what: str, shape=None, prepared: bool = False) -> None:
     free = _pinned_free.get(status.numel())
     host = free.pop() if free else torch.empty(status.shape, dtype=status.dtype, pin_memory=True)
     host.copy_(status, non_blocking=True)
     event = torch.cuda.Event()
     event.record()
-    _pending_checks.append((host, event, what, shape))
+    _pending_checks.append((host, event, what, shape, prepared))
 
 
 class _ConeLossFunction(torch.autograd.Function):
@@ -136,6 +151,13 @@ class _ConeLossFunction(torch.autograd.Function):
         if lazy:
             _poll_checks()  # the verdicts of earlier calls that have arrived
             kwargs = dict(kwargs, check=False)
+        if isinstance(tight_ctrs, PreparedCones):
+            from . import qpsolver
+
+            if qpsolver._step_ok.get(tight_ctrs.shape[1:]) is False:
+                # prepared before a verdict said that this shape holds cones the step kernel does not take (_examine):
+                # the dense tensor it keeps goes down the general path, status-checked until a tier has settled
+                tight_ctrs = tight_ctrs.ctrs
         if warm is not None and (mode not in _WARM_MODES or isinstance(tight_ctrs, SparseCones)):
             warm = None  # (a batch on the sparse wire format runs cold)
         if warm is not None and not isinstance(tight_ctrs, (PackedBatch, PreparedCones)) and _warm_dense_ok(tight_ctrs, kwargs) \
@@ -171,7 +193,7 @@ class _ConeLossFunction(torch.autograd.Function):
                 _defer_check(o["status"], "solver='hip' (lazy check, sparse cones)", (tight_ctrs.m_max, tight_ctrs.d))
             else:
                 shape = None if isinstance(tight_ctrs, PackedBatch) else (int(tight_ctrs.shape[1]), int(tight_ctrs.shape[2]))
-                _defer_check(o["status"], "solver='hip' (lazy check)", shape)
+                _defer_check(o["status"], "solver='hip' (lazy check)", shape, prepared=isinstance(tight_ctrs, PreparedCones))
             # the verdict arrives a call or two late: until then a failed instance (NaN-filled outputs) must not reach
             # the optimizer.  The step kernel zeroes its loss and gradient itself (CAVE_STEP_ZERO_FAILED); after the
             # other kernels it is masked here, on the device (no host sync either way)

@@ -373,29 +373,7 @@ int32_t cave_hip_pack_large_sparse(const cave_sparse_cones* cones, int64_t nnz_c
 
 // ------------------------------------------------------------------ fused step
 
-static int32_t step_limits(int64_t m_max, int64_t d, int32_t& cap, int32_t& lds) {
-  if (m_max < 0 || d <= 0 || d > kLiteMaxD || m_max > 32767) return CAVE_E_INVALID;
-  cap = 0;
-  uint64_t pack_lds = 0;
-  if (m_max > 0) {
-    // non-zeros kept per instance: structured cones carry <= d unit entries + a few sparse rows (cone_instance.h
-    // default_limits); the arena of the two-wave pack half: no dump slots behind the scan output, no prediction
-    int64_t c = 4 * (m_max + d) + 128;
-    if (c > m_max * d) c = m_max * d;
-    if (c < 64) c = 64;
-    cap = (int32_t)c;
-    pack_lds = arena_bytes_dense(m_max, d, c, 64, 32, c * 6 / 10, 0, true, false) - align8u(4 * d);
-  }
-  const uint32_t solve_lds = step_solve_lds_bytes(d);
-  uint32_t need = pack_lds > solve_lds ? (uint32_t)pack_lds : solve_lds;
-  need = (need + 255u) & ~255u;
-  // four solve blocks + two pack blocks per compute unit: the fused form only pays when six workgroups fit
-  // (a launch without a pack half -- m_max = 0: the lite slots of a device-resident store -- needs four)
-  if ((uint64_t)need * (m_max > 0 ? 6u : 4u) > kMaxLds) return CAVE_E_INVALID;
-  lds = (int32_t)need;
-  return CAVE_OK;
-}
-
+// (step_limits, the launch limits of a shape: cone_step.h)
 int32_t cave_hip_step_lds_bytes(int64_t m_max, int64_t d) {
   int32_t cap = 0, lds = 0;
   const int32_t rc = step_limits(m_max, d, cap, lds);
@@ -444,7 +422,7 @@ static int32_t cone_step_impl(const cave_lite_store* solve, const int64_t* ids, 
     if (!lite_store_ok(next, B_next, d)) return fail(CAVE_E_INVALID, "cone_step: bad next store (size, d, null or unaligned array)");
     if (B > 0 && next->hdr == solve->hdr) return fail(CAVE_E_INVALID, "cone_step: solve and next must be different stores");
     P.Q.ctrs = next_ctrs; P.Q.B = B_next; P.Q.m = (int32_t)m_max; P.Q.d = (int32_t)d; P.Q.nnz_cap = (uint32_t)cap;
-    P.Q.store = *next; P.Q.status = pack_status;
+    P.Q.store = *next; P.Q.status = pack_status; P.Q.lite_pmax = lite_pmax_table((int)d);
   }
   P.lds_bytes = (uint32_t)lds;
   P.tickets = cu_tickets;
@@ -454,8 +432,8 @@ static int32_t cone_step_impl(const cave_lite_store* solve, const int64_t* ids, 
     static_cast<StepParams&>(PW) = P;
     PW.W.key = warm->key; PW.W.theta = warm->theta; PW.W.n = warm->n_entries; PW.W.keys = keys; PW.W.hit = warm_hit;
     // the LDS copy of a hit's multipliers beyond both arenas, when the launch keeps its residency with it
-    const uint32_t extra = 256u;
-    if ((uint64_t)(lds + extra) * (B_next > 0 ? 6u : 4u) <= kMaxLds) { PW.W.lds_extra = extra; PW.lds_bytes += extra; }
+    PW.W.lds_extra = step_warm_lds_extra((uint32_t)lds, B_next > 0);
+    PW.lds_bytes += PW.W.lds_extra;
     hipError_t e = launch_step_warm((unsigned)(B + B_next), PW.lds_bytes, (hipStream_t)stream, PW);
     if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch cone_step_kernel (warm)", e);
     return CAVE_OK;
@@ -492,12 +470,10 @@ int32_t cave_hip_lite_from_packed(const cave_cone_store* src, const cave_lite_st
   if (src->n < 0 || src->n >= (int64_t)1 << 31 || src->d <= 0 || src->d > kLiteMaxD)
     return fail(CAVE_E_INVALID, "lite_from_packed: need 0 < d <= 256, n < 2^31");
   if (!lite_store_ok(dst, src->n, src->d)) return fail(CAVE_E_INVALID, "lite_from_packed: bad lite store (size, d, null or unaligned array)");
-  const int64_t d = src->d;
-  const uint64_t lds = 256 + 64 + align8u(4 * d) + align8u(d) + align8u(4 * (d + 1)) + align8u(4 * (kLiteMaxRows + 1)) + 64 +
-                       2 * align8u(2 * 64 * kLiteMaxChunk) + lite_lds_bytes((int)d, 64u * kLiteMaxChunk) + 64;
+  const uint32_t lds = lite_from_packed_lds_bytes(src->d);
   LiteFromPackedParams P;
-  P.src = *src; P.dst = *dst; P.n = src->n; P.lds_bytes = (uint32_t)lds; P.status = status;
-  hipError_t e = launch_lite_from_packed((unsigned)src->n, (uint32_t)lds, (hipStream_t)stream, P);
+  P.src = *src; P.dst = *dst; P.n = src->n; P.lds_bytes = lds; P.status = status; P.lite_pmax = lite_pmax_table((int)src->d);
+  hipError_t e = launch_lite_from_packed((unsigned)src->n, lds, (hipStream_t)stream, P);
   if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch lite_from_packed_kernel", e);
   return CAVE_OK;
 }

@@ -230,7 +230,7 @@ CAVE_HD SolveView view_of(const ConeBuild& cb) {
 
 // hot-first allocation of the large-cone path: LDS while it lasts, then the global workspace
 #ifdef CAVE_EMUL_COUNTERS
-inline long* emul_counters() {  // test builds only: [0] dense path, [1] one-wave band path, [2] lite path, [3] H-free band, [4] lite with bound rows, [5] red-black reduction of the band
+inline long* emul_counters() {  // test builds only: [0] dense path, [1] one-wave band path, [2] lite path, [3] H-free band, [4] lite with bound rows, [5] red-black reduction of the band, [6] lite solver of the step kernel's solve half (cone_step.h)
   static long cnt[8] = {0};
   return cnt;
 }

@@ -44,6 +44,7 @@ struct StepPackParams {
   uint32_t nnz_cap;
   cave_lite_store store;
   int32_t* status;
+  uint64_t lite_pmax;   // lite_pmax_table(d): most reduced rows a cone with nI = 1 .. 8 bound rows may have (byte nI - 1)
 };
 
 // Multiplier cache of the warm solve half (cave_warm_cache, include/cave_hip.h): n entries of one 64-bit key and 32
@@ -106,14 +107,113 @@ static inline uint32_t step_solve_lds_bytes(int64_t d) {
   return (uint32_t)((s + 255u) & ~255ull);
 }
 
+// Scratch of lite_model_step (cone_core.h) for p reduced rows of which nI have bounds, in doubles: XS [p * nI],
+// S [nI * (nI | 1)], four vectors of nI, flags
+CAVE_HOSTDEV uint32_t lite_scratch_doubles(int p, int nI) { return (uint32_t)(p * nI + nI * (nI | 1) + 4 * nI + (nI + 7) / 8); }
+
+// Does the solve half find that scratch for a cone of p reduced rows, nI of them with bounds?  It takes the epilogue's
+// target vector (d doubles, idle while the solver runs) when that is big enough, else a block of its own behind its
+// other arrays -- and step_solve_lds_bytes has no term for such a block: what is there is what the arrays sized by p
+// leave of their p = 32 figures.  The smallest arena a solve can meet is that of a launch without a pack half
+// (step_solve_lds_bytes(d): a fused launch has max(pack, solve)), so the allocations of run_lite_instance are replayed
+// against it here, for the mode that allocates most (INNER: the average normal too) and 24 csr16 entries per lane.
+// write_lite_slot refuses a cone that fails this (its slot says -1 and the host takes the general operator), so a slot
+// that says 1 is solved by every launch form.  At d = 256: p = 32 with up to 5 bound rows, p <= 31 with 6, p <= 28
+// with 7, p <= 27 with 8.  Host code: the kernels get the rule as a table (lite_pmax_table), one compare per cone.
+static inline bool lite_scratch_fits(int d, int p, int nI) {
+  const uint32_t need = lite_scratch_doubles(p, nI);
+  if (need <= (uint32_t)d) return true;
+  const uint32_t pp = (uint32_t)(p > 0 ? p : 1), ud = (uint32_t)d;
+  uint32_t off = 0;
+  auto take = [&off](uint32_t bytes, uint32_t align) { off = ((off + align - 1u) & ~(align - 1u)) + bytes; };
+  take(4u * ud, 8u); take(4u * ud, 8u); take(ud, 8u); take(4u * (pp + 1u), 8u); take(pp, 8u);   // y, avg, usign, mptr, vkind
+  take(16u * ud, 16u); take(4u * (uint32_t)kLiteCsrWords, 16u); take(8u * (33u + 64u + 65u), 8u); take(40u, 8u);  // ell, csr16, rs, rl
+  take(8u * ud, 8u); take(8u * ud, 8u); take(8u * (ud + 1u), 8u); take(4u * ud, 8u);            // res, tvec, rc, wold
+  take(8u * 33u, 8u); take(8u * 33u, 8u);                                                        // theta, dv
+  for (int i = 0; i < 5; ++i) take(8u * pp, 8u);                                                 // ttry, told, g, g2, step
+  take(8u * (uint32_t)(p > 0 ? p * (p | 1) : 1), 8u); take(pp, 8u);                              // H, act
+  take(8u * need, 8u);
+  return off <= ((step_solve_lds_bytes(d) - kStepElectBytes) & ~7u);
+}
+
+// The rule as the kernels read it (StepPackParams / LiteFromPackedParams::lite_pmax): byte nI - 1 holds the most reduced
+// rows a cone with nI bound rows may have at dimension d (the need grows with p, so the accepted p are an interval from
+// nI up; 0 = none).  A cone without bound rows needs no scratch.
+// (Evaluated once per process for every d: a launch costs a table look-up on the host.)
+struct LitePmaxTables {
+  uint64_t t[kLiteMaxD + 1];
+  LitePmaxTables() {
+    t[0] = 0;
+    for (int d = 1; d <= kLiteMaxD; ++d) {
+      uint64_t x = 0;
+      for (int nI = 1; nI <= 8; ++nI) {
+        int pmax = 0;
+        for (int p = nI; p <= kLiteMaxRows && lite_scratch_fits(d, p, nI); ++p) pmax = p;
+        x |= (uint64_t)pmax << (8 * (nI - 1));
+      }
+      t[d] = x;
+    }
+  }
+};
+static inline uint64_t lite_pmax_table(int d) {
+  static const LitePmaxTables tabs;
+  return d >= 1 && d <= kLiteMaxD ? tabs.t[d] : 0;
+}
+CAVE_HOSTDEV bool lite_pmax_allows(uint64_t table, int p, int nI) {
+  return nI == 0 || p <= (int)((table >> (8 * (nI - 1))) & 0xffu);
+}
+
+// Launch limits of the fused step for dense batches of shape (m_max, d) (m_max = 0: a launch without a pack half -- the
+// lite slots of a device-resident store): non-zeros kept per instance by the pack half and the dynamic LDS per
+// workgroup; CAVE_E_INVALID when the shape does not qualify.  Host code (cave_hip.hip and the emulation build of
+// tests/emul size their launches from this one function).
+static inline int32_t step_limits(int64_t m_max, int64_t d, int32_t& cap, int32_t& lds) {
+  if (m_max < 0 || d <= 0 || d > kLiteMaxD || m_max > 32767) return CAVE_E_INVALID;
+  cap = 0;
+  uint64_t pack_lds = 0;
+  if (m_max > 0) {
+    // non-zeros kept per instance: structured cones carry <= d unit entries + a few sparse rows (cone_instance.h
+    // default_limits); the arena of the two-wave pack half: no dump slots behind the scan output, no prediction
+    int64_t c = 4 * (m_max + d) + 128;
+    if (c > m_max * d) c = m_max * d;
+    if (c < 64) c = 64;
+    cap = (int32_t)c;
+    pack_lds = arena_bytes_dense(m_max, d, c, 64, 32, c * 6 / 10, 0, true, false) - align8u(4 * d);
+  }
+  const uint32_t solve_lds = step_solve_lds_bytes(d);
+  uint32_t need = pack_lds > solve_lds ? (uint32_t)pack_lds : solve_lds;
+  need = (need + 255u) & ~255u;
+  // four solve blocks + two pack blocks per compute unit: the fused form only pays when six workgroups fit
+  // (a launch without a pack half -- m_max = 0: the lite slots of a device-resident store -- needs four)
+  if ((uint64_t)need * (m_max > 0 ? 6u : 4u) > kMaxLds) return CAVE_E_INVALID;
+  lds = (int32_t)need;
+  return CAVE_OK;
+}
+
+// LDS bytes the warm variant adds behind both arenas of a launch of `lds` bytes per workgroup (the LDS copy of a hit's
+// multipliers, StepWarm::lds_extra): 256 when the launch keeps its residency with them -- six workgroups per compute
+// unit with a pack half, four without --, else 0 (the copy is then taken from the solve arena if there is room)
+static inline uint32_t step_warm_lds_extra(uint32_t lds, bool has_pack) {
+  const uint32_t extra = 256u;
+  return (uint64_t)(lds + extra) * (has_pack ? 6u : 4u) <= kMaxLds ? extra : 0u;
+}
+
+// dynamic LDS of one workgroup of lite_from_packed_kernel (cost dimension d; any cone the lite solver takes)
+static inline uint32_t lite_from_packed_lds_bytes(int64_t d) {
+  const uint64_t lds = 256 + 64 + align8u(4 * d) + align8u(d) + align8u(4 * (d + 1)) + align8u(4 * (kLiteMaxRows + 1)) + 64 +
+                       2 * align8u(2 * 64 * kLiteMaxChunk) + lite_lds_bytes((int)d, 64u * kLiteMaxChunk) + 64;
+  return (uint32_t)lds;
+}
+
 // -------------------------------------------------------------------------------------------------- pack half
 // Eligibility + lite index structures of one cone (SolveView in LDS, `avg` its average normal) -> slot `slot` of the
 // lite store.  hdr[0] = 1: the slot holds a cone the one-wave solver takes;  -1: it does not (not +-1, more than 32
-// reduced rows / 8 entries per column / 8 bound rows, rows not ordered [free | bound], or no room in the arena): the
+// reduced rows / 8 entries per column / 8 bound rows, rows not ordered [free | bound], no room in the arena, or no room
+// for the active-set scratch in the solve half's arena: lite_scratch_fits): the
 // solve half reports CAVE_ST_TOO_LARGE for it and the host falls back to the general operator.  Returns the state.
 template <class C>
 CAVE_HD int32_t write_lite_slot(C& c, Arena& ar, const SolveView& v, const float* avg, uint32_t nnzM, const cave_lite_store& S,
-                                int64_t slot) {
+                                int64_t slot, uint64_t lite_pmax) {
   const int NT = C::NT;
   const int d = v.d, p = v.p;
   int nF = 0;
@@ -127,7 +227,7 @@ CAVE_HD int32_t write_lite_slot(C& c, Arena& ar, const SolveView& v, const float
     for (int i = c.tid(); i < p; i += NT) bad += ((v.vkind[i] != 0) != (i < (int)nfree)) ? 1u : 0u;
     bad = c.reduce_add_u32(bad);
     const int nI = p - (int)nfree;
-    ok = bad == 0u && nI <= 8;  // (the solve half finds room for lite_model_step's scratch or reports TOO_LARGE)
+    ok = bad == 0u && nI <= 8 && lite_pmax_allows(lite_pmax, p, nI);  // (a slot that says 1 is one every launch form solves)
     nF = (int)nfree;
     if (ok) ok = lite_build(c, ar, v, L);
   }
@@ -179,7 +279,7 @@ CAVE_HD void run_pack_lite_instance(C& c, unsigned char* smem, uint32_t lds_byte
     compute_avg(c, cb, avg);
     ar.release_top();  // build-phase temporaries are dead now
     const SolveView v = view_of(cb);
-    if (write_lite_slot(c, ar, v, avg, cb.nnzM, S, b) != 1) st = ST_TOO_LARGE;
+    if (write_lite_slot(c, ar, v, avg, cb.nnzM, S, b, P.lite_pmax) != 1) st = ST_TOO_LARGE;
   } else if (c.tid() == 0) {
     int32_t* h = S.hdr + b * kLiteHdr;
     h[0] = -1;
@@ -197,6 +297,7 @@ struct LiteFromPackedParams {
   int64_t n;
   uint32_t lds_bytes;
   int32_t* status;
+  uint64_t lite_pmax;   // lite_pmax_table(src.d)
 };
 template <class C>
 CAVE_HD void run_lite_from_packed(C& c, unsigned char* smem, const LiteFromPackedParams& P, int64_t slot) {
@@ -232,7 +333,7 @@ CAVE_HD void run_lite_from_packed(C& c, unsigned char* smem, const LiteFromPacke
       v.mptr = mptr; v.mcol = mcol; v.mval = nullptr; v.vkind = vkind;
       v.cptr = cptr; v.cvar = cvar; v.cvalc = nullptr; v.usign = usign;
       v.nlong = 0; v.longrow = nullptr;
-      state = write_lite_slot(c, ar, v, avg, nz, P.dst, slot);
+      state = write_lite_slot(c, ar, v, avg, nz, P.dst, slot, P.lite_pmax);
     }
   }
   if (state != 1 && c.tid() == 0) {
@@ -414,7 +515,7 @@ CAVE_HD void run_lite_instance(SC& sc, unsigned char* smem, uint32_t lds_bytes, 
       // scratch of lite_model_step: the epilogue's target vector (idle while the solver runs) when it is big enough,
       // else a block of its own (small cost dimensions: the arena is sized for d = 256)
       const int nI = p - nF;
-      const uint32_t need = (uint32_t)(p * nI + nI * (nI | 1) + 4 * nI + (nI + 7) / 8);
+      const uint32_t need = lite_scratch_doubles(p, nI);
       double* scr = need <= (uint32_t)d ? w.q : ar.try_get<double>(need);
       // (warm: the hit's multipliers in LDS -- lane i < 32 stores theta_i and the solver's lane i reads it back: no sync --
       //  beyond the arena, or after every cold allocation: a miss sees the arena of the cold kernel; no room = a miss)
@@ -436,6 +537,9 @@ CAVE_HD void run_lite_instance(SC& sc, unsigned char* smem, uint32_t lds_bytes, 
         w.dn.on = false;
         w.gen.on = false;
         sc.lite.ell = ell; sc.lite.csr16 = csr16; sc.lite.rs = rs; sc.lite.rl = rl; sc.lite.chn8 = chn8; sc.lite.cmax = cmax;
+#ifdef CAVE_EMUL_COUNTERS
+        if (lane == 0) ++emul_counters()[6];  // test builds: instances the solve half ran the lite solver for
+#endif
         const SolveResult r = solve_cone_impl<SC, true, false>(sc, v, w, P.max_iter, 1e-11);
         st = r.status;
         f = r.f;

@@ -248,6 +248,12 @@ int32_t cave_hip_cone_packed_large(const cave_cone_store* store, const int64_t* 
 /* ------------------------------------------------------------------ fused step (v9)
  * Small +-1 cones on the dense wire format (TSP-20, small grids: d <= 256, <= 32 reduced rows in the order
  * [free | <= 8 bound rows], <= 8 entries per column, <= 1536 non-zeros -- what the one-wave solver takes).
+ * One more condition ties the bound rows to the rows: the active-set loop needs p nI + nI (nI | 1) + 4 nI + 1 doubles of
+ * scratch for p reduced rows of which nI have bounds; they come from a d-vector that is idle during the solve when that
+ * is big enough, else from what the p-sized arrays leave of their 32-row figures in the arena of a solve-only launch.
+ * A cone for which neither holds is refused like one beyond the limits above (slot state -1, pack status
+ * CAVE_ST_TOO_LARGE), so a slot whose state is 1 is solved by every launch form.  At d = 256 this admits 32 rows with
+ * up to 5 bound rows, 31 with 6, 28 with 7, 27 with 8 (TSP-20: 20 + <= 5).
  *
  * A step on the dense format is  (a) stream the dense block + build the reduced cone  ->  (b) Newton solve + loss +
  * gradient.  (a) depends on the cones only, and the training loop has the cones of batch i+1 before it has the
@@ -280,7 +286,11 @@ typedef struct cave_lite_store {
 } cave_lite_store;
 
 /* dynamic LDS per workgroup of cave_hip_cone_step for dense batches of shape (m_max, d); <= 0: the shape does not
- * qualify (d > 256, or five workgroups would not fit a compute unit: use the general operators) */
+ * qualify: d > 256, or SIX workgroups of that size (four solve blocks + two pack blocks) would not fit the 160 KiB of a
+ * compute unit -- use the general operators.  m_max = 0 asks for a launch without a pack half (the lite slots of a
+ * device-resident store), which needs four.  At d = 256 the solve half alone takes 28672 bytes, so from d = 229 on
+ * there is no fused launch whatever m_max: such cones reach the one-wave solver through cave_hip_lite_from_packed and
+ * the solve-only launch. */
 int32_t cave_hip_step_lds_bytes(int64_t m_max, int64_t d);
 
 /* Solve half: B instances of `solve` -- slot ids[b], or slot b when ids is NULL (a transient per-batch store packed

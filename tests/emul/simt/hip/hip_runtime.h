@@ -323,6 +323,7 @@ template <class T> inline T atomic_add(T* p, T v) { T o = *p; *p = o + v; return
 struct float4 { float x, y, z, w; };
 struct uint4 { unsigned x, y, z, w; };
 static inline float4 make_float4(float x, float y, float z, float w) { return float4{x, y, z, w}; }
+static inline uint4 make_uint4(unsigned x, unsigned y, unsigned z, unsigned w) { return uint4{x, y, z, w}; }
 #define threadIdx (::simt::Dim3{(unsigned)::simt::tid(), 0u, 0u})
 #define blockIdx (::simt::S().block_idx)
 #define gridDim (::simt::S().grid_dim)
@@ -330,6 +331,8 @@ static inline float4 make_float4(float x, float y, float z, float w) { return fl
 static inline void __syncthreads() { ::simt::block_sync(); }
 static inline uint64_t __ballot(bool p) { return ::simt::ballot(p); }
 static inline int __popcll(uint64_t x) { return __builtin_popcountll(x); }
+static inline int __ffs(unsigned x) { return __builtin_ffs((int)x); }
+static inline int __ffsll(unsigned long long x) { return __builtin_ffsll((long long)x); }
 static inline double __hiloint2double(int hi, int lo) {
   uint64_t u = ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
   double d;

@@ -6,6 +6,12 @@
 // barrier a rendezvous.  Runs under -fsanitize=address,undefined in the CPU test tier.  Exports cave_simt_* with the
 // signatures of include/cave_hip.h (host pointers, no stream, + a schedule seed: 0 = round robin, else the lanes
 // between two rendezvous run in a seeded random order).  Never loaded by cave_amd.
+//
+// The fused step kernel (cone_step.h) is here too: its pack half (run_pack_lite_instance on the two-wave context the
+// product instantiates), its solve half (run_lite_instance<SoloCtx<32, 4>, WARM>, cold and with the multiplier cache)
+// and run_lite_from_packed, with the LDS figures of the product's own step_limits / lite_from_packed_lds_bytes.  NOT
+// emulated: the wave election of a solve block (kernels.h step_elect_wave reads hardware registers) and the wave
+// priorities; the solve entry calls run_lite_instance behind the election words exactly as the kernel wrapper does.
 #define CAVE_SIMT_EMUL 1
 #define CAVE_EMUL_COUNTERS 1
 #include <hip/hip_runtime.h>
@@ -18,6 +24,7 @@
 #include "../../cave_amd/csrc/ctx_wave.h"
 #include "../../cave_amd/csrc/ctx_block.h"
 #include "../../cave_amd/csrc/cone_instance.h"
+#include "../../cave_amd/csrc/cone_step.h"
 
 using namespace cave;
 
@@ -29,6 +36,8 @@ using Ctx4 = BlockCtx<4>;
 using CtxW = BlockCtx<4, true>;
 using CtxL = BlockCtx<4, true>;
 using CtxL2 = BlockCtx<2, true>;
+using CtxStep = BlockCtx<2, true>;  // pack half of the step kernel (k_step.hip)
+using CtxSolo = SoloCtx<32, 4>;      // its solve half: one wave
 
 struct Lds {  // exact-size, 16-byte aligned heap block standing in for the workgroup's LDS: ASan sees overruns
   std::vector<unsigned char> raw;
@@ -39,7 +48,13 @@ struct Lds {  // exact-size, 16-byte aligned heap block standing in for the work
     p = raw.data() + off;
     raw.resize(off + n);  // no slack behind the arena
     p = raw.data() + off;
+    len = n;
   }
+  size_t len;
+  // LDS is not cleared between workgroups: a block starts on whatever the last one left there.  The step entries
+  // poison the block before every workgroup (0xFF bytes: NaN as a double or float, 65535 as an index), so that a
+  // read of LDS the workgroup has not written shows up as a wrong result instead of a convenient zero
+  void poison() { memset(p, 0xFF, len); }
 };
 
 template <class C, class F>
@@ -95,9 +110,108 @@ int32_t packed_large_impl(const PackedParams& P, int64_t slice_bytes, uint64_t s
   return CAVE_OK;
 }
 
+// solve half of the step kernel: one 64-lane wave per instance.  `lds` is the launch's LDS without the warm variant's
+// extra block, `extra` that block (kernels.h cone_step_kernel: lds_bytes -= W.lds_extra; smem + kStepElectBytes)
+template <bool WARM>
+void step_solve_impl(const StepSolveParams& P, const StepWarm& W, uint32_t lds, uint32_t extra, uint64_t seed) {
+  Lds mem((size_t)lds + extra);
+  launch<CtxSolo>(P.B, (unsigned)P.B, seed, [&](int64_t b) {
+    if (simt::tid() == 0) mem.poison();
+    simt::block_sync();
+    CtxSolo sc;
+    sc.lane = simt::lane();
+    run_lite_instance<CtxSolo, WARM>(sc, mem.p + kStepElectBytes, lds - kStepElectBytes, P, b, W);
+  });
+}
+
+bool lite_store_ok(const cave_lite_store* s, int64_t need, int64_t d) {  // (as cave_hip.hip)
+  return s && s->n >= need && s->d == d && s->hdr && s->usign && s->avg && s->rowptr && s->ell && s->csr16 && s->rl &&
+         (((uintptr_t)s->ell | (uintptr_t)s->csr16) & 15u) == 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+// ---- fused step (cone_step.h)
+int32_t cave_simt_step_lds_bytes(int64_t m_max, int64_t d) {  // what cave_hip_step_lds_bytes returns
+  int32_t cap = 0, lds = 0;
+  const int32_t rc = step_limits(m_max, d, cap, lds);
+  return rc == CAVE_OK ? lds : rc;
+}
+int32_t cave_simt_step_solve_lds_bytes(int64_t d) { return (int32_t)step_solve_lds_bytes(d); }
+int32_t cave_simt_step_warm_lds_extra(int32_t lds, int32_t has_pack) { return (int32_t)step_warm_lds_extra((uint32_t)lds, has_pack != 0); }
+// the rule by which write_lite_slot accepts a cone of p reduced rows, nI of them with bounds (cone_step.h)
+int32_t cave_simt_lite_scratch_fits(int32_t d, int32_t p, int32_t nI) {
+  return (lite_scratch_fits(d, p, nI) ? 1 : 0) | (lite_pmax_allows(lite_pmax_table(d), p, nI) ? 2 : 0);  // bit 0: the rule, bit 1: as the kernels read it
+}
+int32_t cave_simt_lite_from_packed_lds_bytes(int64_t d) { return (int32_t)lite_from_packed_lds_bytes(d); }
+uint64_t cave_simt_lite_content_key(uint32_t fp, int32_t p, int32_t nF, uint32_t nnz) { return lite_content_key(fp, p, nF, nnz); }
+
+// pack half: instances [0, B) of ctrs [B, m_max, d] into slots [0, B) of `dst`; LDS and non-zero cap of the product
+int32_t cave_simt_step_pack(const float* ctrs, int64_t B, int64_t m_max, int64_t d, uint64_t seed,
+                            const cave_lite_store* dst, int32_t* status) {
+  int32_t cap = 0, lds = 0;
+  if (B < 0 || m_max <= 0 || step_limits(m_max, d, cap, lds) != CAVE_OK || !lite_store_ok(dst, B, d)) return CAVE_E_INVALID;
+  StepPackParams Q;
+  Q.ctrs = ctrs; Q.B = B; Q.m = (int32_t)m_max; Q.d = (int32_t)d; Q.nnz_cap = (uint32_t)cap; Q.store = *dst; Q.status = status;
+  Q.lite_pmax = lite_pmax_table((int)d);
+  Lds mem((size_t)lds);
+  launch<CtxStep>(B, (unsigned)B, seed, [&](int64_t b) {
+    if (simt::tid() == 0) mem.poison();
+    simt::block_sync();
+    CtxStep c;
+    c.init(mem.p);
+    run_pack_lite_instance(c, mem.p, (uint32_t)lds, Q, b);
+  });
+  return CAVE_OK;
+}
+
+// solve half.  lds_bytes: LDS of the launch (a value of cave_simt_step_lds_bytes); lds_extra: the warm variant's block
+// behind it (cave_hip.hip: 256 when the residency allows it, else 0).  warm == NULL: the cold kernel.
+int32_t cave_simt_step_solve(const cave_lite_store* solve, const int64_t* ids, const float* pred, int64_t B, int32_t mode,
+                             float sign, float inner_ratio, int32_t max_iter, int32_t flags, int32_t lds_bytes,
+                             int32_t lds_extra, const cave_warm_cache* warm, const int64_t* keys, uint8_t* warm_hit,
+                             uint64_t seed, float* proj, float* rnorm, float* target, float* loss, float* grad,
+                             int32_t* status, int32_t* iters) {
+  if (B < 0 || mode < CAVE_MODE_PROJECT || mode > CAVE_MODE_AVG || (!pred && mode != CAVE_MODE_AVG)) return CAVE_E_INVALID;
+  if (!solve || !lite_store_ok(solve, ids ? 1 : B, solve->d)) return CAVE_E_INVALID;
+  if (lds_bytes <= (int32_t)kStepElectBytes || lds_extra < 0) return CAVE_E_INVALID;
+  StepSolveParams P;
+  P.store = *solve; P.ids = ids; P.pred = pred; P.B = B; P.mode = mode; P.sign = sign; P.inner_ratio = inner_ratio;
+  P.max_iter = max_iter > 0 ? max_iter : 100;
+  P.flags = flags;
+  P.o = OutPtrs{proj, rnorm, target, loss, grad, status, iters};
+  StepWarm W{};
+  if (warm) {
+    const int64_t n = warm->n_entries;
+    if (n <= 0 || (n & (n - 1)) != 0 || !warm->key || !warm->theta || ((uintptr_t)warm->theta & 15u) != 0) return CAVE_E_INVALID;
+    W.key = warm->key; W.theta = warm->theta; W.n = n; W.keys = keys; W.hit = warm_hit; W.lds_extra = (uint32_t)lds_extra;
+    step_solve_impl<true>(P, W, (uint32_t)lds_bytes, (uint32_t)lds_extra, seed);
+  } else {
+    if (warm_hit) memset(warm_hit, 0, (size_t)B);
+    step_solve_impl<false>(P, W, (uint32_t)lds_bytes, 0u, seed);
+  }
+  return CAVE_OK;
+}
+
+// slot i of `dst` from slot i of the packed store `src` (lite_from_packed_kernel<Ctx2>)
+int32_t cave_simt_lite_from_packed(const cave_cone_store* src, const cave_lite_store* dst, int32_t* status, uint64_t seed) {
+  if (!src || !dst || src->n < 0 || src->d <= 0 || src->d > kLiteMaxD || !lite_store_ok(dst, src->n, src->d)) return CAVE_E_INVALID;
+  LiteFromPackedParams P;
+  P.src = *src; P.dst = *dst; P.n = src->n; P.lds_bytes = lite_from_packed_lds_bytes(src->d); P.status = status;
+  P.lite_pmax = lite_pmax_table((int)src->d);
+  Lds mem((size_t)P.lds_bytes);
+  launch<Ctx2>(P.n, (unsigned)P.n, seed, [&](int64_t b) {
+    if (simt::tid() == 0) mem.poison();
+    simt::block_sync();
+    Ctx2 c;
+    c.init(mem.p);
+    run_lite_from_packed(c, mem.p, P, b);
+  });
+  return CAVE_OK;
+}
+
 
 void cave_simt_path_counters(long* out) {
   for (int i = 0; i < 8; ++i) { out[i] = emul_counters()[i]; emul_counters()[i] = 0; }

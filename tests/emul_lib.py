@@ -206,13 +206,63 @@ class Emul:
         return out
 
 
+# ---- the fused step kernel (cave_amd/csrc/cone_step.h) under the SIMT emulation
+class LiteStore(C.Structure):
+    """struct cave_lite_store (include/cave_hip.h), host arrays."""
+    _fields_ = [
+        ("n", C.c_int64), ("d", C.c_int32), ("reserved", C.c_int32),
+        ("hdr", C.c_void_p), ("usign", C.c_void_p), ("avg", C.c_void_p), ("rowptr", C.c_void_p),
+        ("ell", C.c_void_p), ("csr16", C.c_void_p), ("rl", C.c_void_p),
+    ]
+
+
+class WarmCacheC(C.Structure):
+    """struct cave_warm_cache (include/cave_hip.h), host arrays."""
+    _fields_ = [("n_entries", C.c_int64), ("key", C.c_void_p), ("theta", C.c_void_p)]
+
+
+LITE_HDR, LITE_ROWPTR, LITE_CSR_WORDS, LITE_RL = 8, 33, 768, 32  # per-slot extents of cave_lite_store
+ST_TOO_LARGE, ST_BAD_INPUT, STEP_ZERO_FAILED = 2, 3, 1
+
+
+def _aligned(n, dtype, fill=0):
+    """n elements of dtype on a 16-byte boundary (ell / csr16 / the cache's multipliers)."""
+    item = np.dtype(dtype).itemsize
+    raw = np.zeros(n * item + 16, np.uint8)
+    off = (-raw.ctypes.data) % 16
+    a = raw[off:off + n * item].view(dtype)
+    a[...] = fill
+    return a
+
+
+def lite_store(n, d, fill=0):
+    """An n-slot lite store of host arrays: (struct, {name: array}).  `fill`: a byte pattern for every array (a test
+    then sees what a pack leaves untouched); hdr is zero (state 0: never packed) either way."""
+    arrs = {
+        "hdr": np.zeros(n * LITE_HDR, np.int32),
+        "usign": np.full(n * d, fill, np.uint8),
+        "avg": np.zeros(n * d, np.float32),
+        "rowptr": np.full(n * LITE_ROWPTR, fill * 0x01010101, np.uint32),
+        "ell": _aligned(n * 4 * d, np.uint32, fill * 0x01010101),
+        "csr16": _aligned(n * LITE_CSR_WORDS, np.uint32, fill * 0x01010101),
+        "rl": np.full(n * LITE_RL, fill, np.uint8),
+    }
+    st = LiteStore(n=n, d=d, reserved=0, **{k: v.ctypes.data for k, v in arrs.items()})
+    return st, arrs
+
+
+def warm_cache(n):
+    arrs = {"key": np.zeros(n, np.uint64), "theta": _aligned(n * 32, np.float32)}
+    return WarmCacheC(n_entries=n, key=arrs["key"].ctypes.data, theta=arrs["theta"].ctypes.data), arrs
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # SIMT emulation build (tests/emul/simt_abi.cpp): the GPU-only code paths -- wave contexts, DPP / readlane /
 # ballot primitives, the one-wave lite solver, the one-/two-wave band elimination, the blocked dense LDL^T --
 # compiled by g++ against a shim <hip/hip_runtime.h> in which every lane is a fiber.  TEST INFRASTRUCTURE ONLY.
 _SIMT_SRC = os.path.join(_HERE, "emul", "simt_abi.cpp")
 _SIMT_DEPS = _DEPS + [_SIMT_SRC, os.path.join(_HERE, "emul", "simt", "hip", "hip_runtime.h")] + [
-    os.path.join(_HERE, "..", "cave_amd", "csrc", n) for n in ("wave_prims.h", "ctx_wave.h", "ctx_block.h")]
+    os.path.join(_HERE, "..", "cave_amd", "csrc", n) for n in ("wave_prims.h", "ctx_wave.h", "ctx_block.h", "cone_step.h")]
 
 
 def build_simt(asan: bool = False, defines: tuple = (), tag: str = "") -> str:
@@ -297,6 +347,68 @@ class Simt:
         rc = self.lib.cave_simt_cone_packed_large(
             C.byref(store), _p(ids), _p(pred), C.c_int64(B), C.c_int32(mode), C.c_float(sign), C.c_float(inner_ratio),
             C.c_int32(max_iter), C.c_int32(lds), C.c_int32(waves), C.c_int64(slice_bytes), C.c_uint64(seed),
+            _p(out["proj"]), _p(out["rnorm"]), _p(out["target"]), _p(out["loss"]), _p(out["grad"]),
+            _p(out["status"]), _p(out["iters"]))
+        assert rc == 0, rc
+        return out
+
+    # ---- the fused step kernel (cone_step.h): pack half, solve half (cold / warm), lite_from_packed
+    def step_lds_bytes(self, m_max, d):
+        """cave_hip_step_lds_bytes of the product (the same step_limits): < 0 = the shape has no such launch."""
+        return int(self.lib.cave_simt_step_lds_bytes(C.c_int64(m_max), C.c_int64(d)))
+
+    def lite_scratch_fits(self, d, p, nI):
+        """lite_scratch_fits of cone_step.h: does write_lite_slot accept p reduced rows, nI of them with bounds, at dimension d"""
+        r = int(self.lib.cave_simt_lite_scratch_fits(C.c_int32(d), C.c_int32(p), C.c_int32(nI)))
+        assert r in (0, 3), (d, p, nI, r)   # the rule itself and the table the kernels read say the same
+        return r == 3
+
+    def step_pack(self, ctrs, seed=0, fill=0):
+        """Pack half of the step kernel (run_pack_lite_instance, two waves): -> (store, arrays, pack status [B])."""
+        ctrs = np.ascontiguousarray(ctrs, dtype=np.float32)
+        B, m, d = ctrs.shape
+        st, arrs = lite_store(B, d, fill)
+        status = np.full(B, -7, np.int32)
+        rc = self.lib.cave_simt_step_pack(_p(ctrs), C.c_int64(B), C.c_int64(m), C.c_int64(d), C.c_uint64(seed), C.byref(st),
+                                          _p(status))
+        assert rc == 0, rc
+        return st, arrs, status
+
+    def lite_from_packed(self, store, seed=0, fill=0):
+        """run_lite_from_packed over every slot of a packed store (Emul.pack): -> (lite store, arrays, status [n])."""
+        st, arrs = lite_store(store.n, store.d, fill)
+        status = np.full(store.n, -7, np.int32)
+        rc = self.lib.cave_simt_lite_from_packed(C.byref(store), C.byref(st), _p(status), C.c_uint64(seed))
+        assert rc == 0, rc
+        return st, arrs, status
+
+    def step_solve(self, store, pred, mode, sign=-1.0, inner_ratio=0.2, max_iter=0, ids=None, B=None, flags=0,
+                         lds_bytes=0, m_max=0, warm=None, keys=None, lds_extra=None, seed=0):
+        """Solve half of the step kernel (run_lite_instance on one 64-lane wave per instance).  LDS: `lds_bytes`, or the
+        product's figure for a launch with a pack half of m_max rows (0: solve-only).  warm: a WarmCacheC (the warm kernel;
+        lds_extra as cave_hip.hip chooses it unless given) -> out["warm_hit"]."""
+        d = store.d
+        pred = None if pred is None else np.ascontiguousarray(pred, dtype=np.float32)
+        ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.int64)
+        if B is None:
+            B = len(ids) if ids is not None else (len(pred) if pred is not None else store.n)
+        lds = lds_bytes or self.step_lds_bytes(m_max, d)
+        assert lds > 0, (m_max, d, lds)
+        if lds_extra is None:  # what cave_hip.hip launches the warm kernel with (step_warm_lds_extra, cone_step.h)
+            lds_extra = int(self.lib.cave_simt_step_warm_lds_extra(C.c_int32(lds), C.c_int32(m_max > 0))) if warm is not None else 0
+        keys = None if keys is None else np.ascontiguousarray(keys, dtype=np.int64)
+        out = self._outs(B, d)
+        for k in ("proj", "target", "grad"):   # sentinels: what an instance does not write stays visible
+            out[k][...] = 77.0
+        out["rnorm"][...] = 77.0
+        out["loss"][...] = 77.0
+        out["status"][...] = -7
+        out["iters"][...] = -7
+        out["warm_hit"] = np.full(B, 9, np.uint8)
+        rc = self.lib.cave_simt_step_solve(
+            C.byref(store), _p(ids), _p(pred), C.c_int64(B), C.c_int32(mode), C.c_float(sign), C.c_float(inner_ratio),
+            C.c_int32(max_iter), C.c_int32(flags), C.c_int32(lds), C.c_int32(lds_extra),
+            None if warm is None else C.byref(warm), _p(keys), _p(out["warm_hit"]), C.c_uint64(seed),
             _p(out["proj"]), _p(out["rnorm"]), _p(out["target"]), _p(out["loss"]), _p(out["grad"]),
             _p(out["status"]), _p(out["iters"]))
         assert rc == 0, rc

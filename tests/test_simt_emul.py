@@ -242,7 +242,7 @@ def test_dense_ldl_with_paused_factorisation_under_emulation(emul, simt, waves):
 def test_simt_build_is_asan_ubsan_clean():
     """The emulated GPU code under AddressSanitizer + UBSan: the LDS arena and the workspace slice are exact-size heap
     blocks, so an index past a window, a ring or a scratch row is reported here (lite solver, both band forms with
-    bound rows, dense LDL^T)."""
+    bound rows, dense LDL^T; the three entry points of the fused step kernel at the lite solver's limits)."""
     import emul_lib
 
     so = emul_lib.build_simt(asan=True)
@@ -268,6 +268,18 @@ def test_simt_build_is_asan_ubsan_clean():
         "c3,y3,_ = synth.tsp_batch(36, 1, 2)\n"
         "st,arrs,mr,mz = E.pack_large(c3); bw = emul_lib.store_bandwidth(arrs, 1, c3.shape[2])\n"
         "for w in (4, 2): S.cone_packed_large(st,arrs,mr,bw,np.arange(1),y3,2,waves=w,seed=w)\n"
+        "import limit_cones as LC\n"   # the step kernel (cone_step.h): a cone at d = 256 / 1536 non-zeros and one refused
+        "for cs in (LC.IN_CASES[0], LC.OUT_CASES[2]):\n"
+        "    assert cs.name in ('d256_16f8b_1536', 'd64_col9')\n"
+        "    bt = LC.batch(cs, 11, B=3)\n"
+        "    st,arrs,mr,mz = E.pack(bt['ctrs'], nnz_cap=LC.dense_nnz(bt['ctrs']) + 64, lds_bytes=160 * 1024)\n"
+        "    ls,la,s2 = S.lite_from_packed(st, seed=3)\n"
+        "    wc,wa = emul_lib.warm_cache(8)\n"
+        "    for w in (None, wc, wc): o = S.step_solve(ls, bt['pred'], 2, warm=w, seed=5)\n"
+        "    assert (o['status'] == 0).sum() == (3 if cs.kind == 'in' else 2), o['status']\n"
+        "    if S.step_lds_bytes(bt['ctrs'].shape[1], cs.d) > 0:\n"
+        "        fs,fa,s3 = S.step_pack(bt['ctrs'], seed=7)\n"
+        "        S.step_solve(fs, bt['pred'], 2, m_max=bt['ctrs'].shape[1], flags=1, seed=9)\n"
         "print('asan-ok', S.path_counters())\n" % (ROOT, os.path.join(ROOT, "tests"), so, os.path.join(ROOT, "tests")))
     env = dict(os.environ, LD_PRELOAD=libasan, ASAN_OPTIONS="detect_leaks=0:detect_stack_use_after_return=0")
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=900)
