@@ -112,9 +112,12 @@ __device__ __forceinline__ void static_for(F&& f) {
 
 // Solve the p x p system whose free rows are rows of (H + delta*I) and whose
 // fixed rows (act) are identity rows:   H_FF x_F + H_FA x_A = rhs_F,  x_A = rhs_A.
-// ONE wave: lane i keeps row i of [H | rhs] in registers; Gauss-Jordan elimination with the pivot row
-// normalised (lane k uses the multiplier (piv - 1) / piv, so x = the right-hand-side column at the end),
-// pivot row broadcast with v_readlane (no LDS traffic, no barriers).
+// ONE wave: lane i keeps row i of [H | rhs] in registers; Gauss-Jordan elimination, pivot row broadcast with
+// v_readlane (no LDS traffic, no barriers).  The pivot row is left as it is (lane k's multiplier is 0) and every lane
+// divides its right-hand side by its own pivot at the end.  Until the solver-level tests (tests/linsys_cases.py) the
+// row was normalised in place with the multiplier (piv - 1) / piv: row_k - ((piv - 1) / piv) row_k carries a rounding
+// error of (piv - 1) ulps of row_k / piv whatever the reciprocal -- a pivot of 374 (a cone row scaled by e^3) cost
+// eight bits of x_k, invisible end to end.
 //
 // What a pivot costs on one wave (measured, tools/micro/gj_bench.hip, prim_bench.hip): a dependent chain of
 // ~140 cycles (v_readlane pair ~19, v_rcp_f64 ~17, each dependent f64 fma ~5.5) + ~15 cycles per remaining
@@ -146,6 +149,7 @@ __device__ __forceinline__ void gj_solve_regs(int lane, PH H, int ldh, PR rhs, P
   }
   h[PM] = live ? rhs[lane] : 0.0;
   uint64_t deadmask = 0;  // pivots that were not positive
+  double myinv = 1.0;     // reciprocal of this lane's own pivot
   static_for<0, PM>([&](auto kc) {
     constexpr int k = decltype(kc)::value;
     if (k < p) {
@@ -155,7 +159,8 @@ __device__ __forceinline__ void gj_solve_regs(int lane, PH H, int ldh, PR rhs, P
       double inv = __builtin_amdgcn_rcp(pv);
       inv = fma(fma(-pv, inv, 1.0), inv, inv);
       deadmask |= ok ? 0ull : (1ull << k);
-      const double num = ok ? h[k] - ((lane == k) ? 1.0 : 0.0) : 0.0;
+      const double num = (ok && lane != k) ? h[k] : 0.0;  // the pivot row itself stays as it is ...
+      myinv = (lane == k) ? inv : myinv;                   // ... and is divided by its pivot at the end
       const double fac = num * inv;
       constexpr int NCOL = PM - k;  // columns k+1 .. PM (PM = right-hand side); columns >= p hold zeros
       static_for<0, (NCOL + G - 1) / G>([&](auto gc) {
@@ -172,12 +177,12 @@ __device__ __forceinline__ void gj_solve_regs(int lane, PH H, int ldh, PR rhs, P
       });
     }
   });
-  if (live) dv[lane] = ((deadmask >> lane) & 1ull) ? 0.0 : h[PM];
+  if (live) dv[lane] = ((deadmask >> lane) & 1ull) ? 0.0 : h[PM] * myinv;
 }
 
 // PARTIAL Gauss-Jordan: only the pivots k < nF are eliminated, from every row, of [H + reg I | rhs] (no fixed rows).
 // With the rows ordered [F | I] the lanes then hold, in their columns j >= nF and the right-hand side:
-//   rows i <  nF:  X_I = H_FF^-1 H_FI  and  x_g = H_FF^-1 rhs_F        (the pivot rows are normalised)
+//   rows i <  nF:  X_I = H_FF^-1 H_FI  and  x_g = H_FF^-1 rhs_F        (once divided by the row's pivot, on store)
 //   rows i >= nF:  S = H_II - H_IF H_FF^-1 H_FI  (Schur complement)  and  rhs_I - H_IF x_g
 // which go to XS[i * nI + (j - nF)] and xg[i] (LDS).  The active-set loop of a Newton step then works on S alone
 // and the rows of F follow by x_F = x_g - X_I x_I: one elimination per Newton iteration however many bounds block
@@ -202,6 +207,7 @@ __device__ __forceinline__ void gj_partial_regs(int lane, const double* H, int l
   }
   h[PM] = live ? rhs[lane] : 0.0;
   uint64_t deadmask = 0;
+  double myinv = 1.0;  // reciprocal of this lane's own pivot (rows >= nF: 1)
   static_for<0, PM>([&](auto kc) {
     constexpr int k = decltype(kc)::value;
     if (k < nF) {
@@ -211,7 +217,8 @@ __device__ __forceinline__ void gj_partial_regs(int lane, const double* H, int l
       double inv = __builtin_amdgcn_rcp(pv);
       inv = fma(fma(-pv, inv, 1.0), inv, inv);
       deadmask |= ok ? 0ull : (1ull << k);
-      const double num = ok ? h[k] - ((lane == k) ? 1.0 : 0.0) : 0.0;
+      const double num = (ok && lane != k) ? h[k] : 0.0;  // the pivot row itself stays as it is ...
+      myinv = (lane == k) ? inv : myinv;                   // ... and is divided by its pivot at the end
       const double fac = num * inv;
       constexpr int NCOL = PM - k;
       static_for<0, (NCOL + G - 1) / G>([&](auto gc) {
@@ -230,10 +237,10 @@ __device__ __forceinline__ void gj_partial_regs(int lane, const double* H, int l
   });
   const bool dead = ((deadmask >> lane) & 1ull) != 0ull;  // (only pivots k < nF can be flagged)
   const int nI = p - nF;
-  if (live) xg[lane] = dead ? 0.0 : h[PM];
+  if (live) xg[lane] = dead ? 0.0 : h[PM] * myinv;
   static_for<0, PM>([&](auto jc) {
     constexpr int j = decltype(jc)::value;
-    if (live && j >= nF && j < p) XS[lane * nI + (j - nF)] = dead ? 0.0 : h[j];
+    if (live && j >= nF && j < p) XS[lane * nI + (j - nF)] = dead ? 0.0 : h[j] * myinv;
   });
 }
 

@@ -25,6 +25,7 @@
 #include "../../cave_amd/csrc/ctx_block.h"
 #include "../../cave_amd/csrc/cone_instance.h"
 #include "../../cave_amd/csrc/cone_step.h"
+#include "../prims/prim_entries.h"
 
 using namespace cave;
 
@@ -124,6 +125,19 @@ void step_solve_impl(const StepSolveParams& P, const StepWarm& W, uint32_t lds, 
   });
 }
 
+// one solver alone (tests/prims/prim_entries.h): the workgroup's LDS is an exact-size block, poisoned before every system
+template <int KIND>
+int32_t prim_impl(const cave_prims::PrimBatch& a, uint64_t seed) {
+  using C = typename cave_prims::PrimCtx<KIND>::type;
+  Lds mem(cave_prims::kind_lds_bytes(KIND, a.p, a.nF, a.bw));
+  launch<C>(a.B, (unsigned)a.B, seed, [&](int64_t b) {
+    if (simt::tid() == 0) mem.poison();
+    simt::block_sync();
+    cave_prims::prim_body<KIND>(mem.p, a, b);
+  });
+  return CAVE_OK;
+}
+
 bool lite_store_ok(const cave_lite_store* s, int64_t need, int64_t d) {  // (as cave_hip.hip)
   return s && s->n >= need && s->d == d && s->hdr && s->usign && s->avg && s->rowptr && s->ell && s->csr16 && s->rl &&
          (((uintptr_t)s->ell | (uintptr_t)s->csr16) & 15u) == 0;
@@ -132,6 +146,27 @@ bool lite_store_ok(const cave_lite_store* s, int64_t need, int64_t d) {  // (as 
 }  // namespace
 
 extern "C" {
+
+// ---- the linear solvers alone (tests/prims/prim_entries.h); seed as everywhere here
+int32_t cave_simt_prim_run(int32_t kind, const cave_prims::PrimBatch* a, uint64_t seed) {
+  if (!a || a->B < 0 || !cave_prims::kind_valid(kind, a->p, a->nF, a->bw, a->n_ex)) return CAVE_E_INVALID;
+  switch (kind) {
+#define CAVE_PRIM_CASE(K) case K: return prim_impl<K>(*a, seed);
+    CAVE_PRIM_KINDS(CAVE_PRIM_CASE)
+#undef CAVE_PRIM_CASE
+  }
+  return CAVE_E_INVALID;
+}
+int64_t cave_simt_prim_info(int32_t kind, int32_t what, int32_t p, int32_t nF, int32_t bw) {  // sizes the caller allocates by
+  using namespace cave_prims;
+  if (!kind_valid(kind, p, nF, bw, 0)) return -1;
+  switch (what) {
+    case 0: return kind_h_entries(kind, p, bw);
+    case 1: return kind_ws_entries(kind, p, bw);
+    case 2: return kind_lds_bytes(kind, p, nF, bw);
+  }
+  return -1;
+}
 
 // ---- fused step (cone_step.h)
 int32_t cave_simt_step_lds_bytes(int64_t m_max, int64_t d) {  // what cave_hip_step_lds_bytes returns

@@ -261,7 +261,8 @@ def warm_cache(n):
 # ballot primitives, the one-wave lite solver, the one-/two-wave band elimination, the blocked dense LDL^T --
 # compiled by g++ against a shim <hip/hip_runtime.h> in which every lane is a fiber.  TEST INFRASTRUCTURE ONLY.
 _SIMT_SRC = os.path.join(_HERE, "emul", "simt_abi.cpp")
-_SIMT_DEPS = _DEPS + [_SIMT_SRC, os.path.join(_HERE, "emul", "simt", "hip", "hip_runtime.h")] + [
+_SIMT_DEPS = _DEPS + [_SIMT_SRC, os.path.join(_HERE, "emul", "simt", "hip", "hip_runtime.h"),
+                      os.path.join(_HERE, "prims", "prim_entries.h")] + [
     os.path.join(_HERE, "..", "cave_amd", "csrc", n) for n in ("wave_prims.h", "ctx_wave.h", "ctx_block.h", "cone_step.h")]
 
 
@@ -352,6 +353,10 @@ class Simt:
         assert rc == 0, rc
         return out
 
+    def prim_run(self, kind, H, rhs, **kw):
+        """one solver alone on a batch of systems (prim_run_host)"""
+        return prim_run_host(self.lib, kind, H, rhs, **kw)
+
     # ---- the fused step kernel (cone_step.h): pack half, solve half (cold / warm), lite_from_packed
     def step_lds_bytes(self, m_max, d):
         """cave_hip_step_lds_bytes of the product (the same step_limits): < 0 = the shape has no such launch."""
@@ -413,6 +418,64 @@ class Simt:
             _p(out["status"]), _p(out["iters"]))
         assert rc == 0, rc
         return out
+
+
+# ---- the linear solvers alone (tests/prims/prim_entries.h): one ABI for the emulation and for tests/prims/_prims.so
+class PrimBatch(C.Structure):
+    """struct PrimBatch (tests/prims/prim_entries.h)."""
+    _fields_ = [
+        ("B", C.c_int64), ("p", C.c_int32), ("nF", C.c_int32), ("bw", C.c_int32), ("n_ex", C.c_int32),
+        ("reg_rel", C.c_double), ("H", C.c_void_p), ("h_stride", C.c_int64), ("rhs", C.c_void_p), ("act", C.c_void_p),
+        ("ex", C.c_void_p), ("x", C.c_void_p), ("M", C.c_void_p), ("m_stride", C.c_int64), ("aux", C.c_void_p),
+        ("ws", C.c_void_p), ("ws_stride", C.c_int64), ("fail", C.c_void_p),
+    ]
+
+
+PRIM_KINDS = {  # enum of prim_entries.h
+    "gj": 0, "gj_lower": 1, "gjs": 2, "gjs_tri": 3, "spd_b2": 4, "spd_b4": 5, "spd_l2": 6, "spd_l4": 7, "spd_solo": 8,
+    "tri_l4": 9, "tri_b4": 10, "tri_b2": 11, "partial": 12, "tableau": 13, "dense_w2": 14, "dense_w4": 15,
+    "bandw1": 16, "bandw2": 17, "band_hot_w1": 18, "band_hot_l2": 19, "band_hot_l4": 20, "band_cold_l4": 21,
+}
+
+
+def prim_m_entries(kind, p, nF):
+    """entries per system of the matrix output M of an entry"""
+    if kind == "partial":
+        return max(1, p * (p - nF))
+    if kind == "tableau":
+        return 72
+    if kind.startswith("dense"):
+        return ((p + 1) // 2) * (p + 1)
+    return 1
+
+
+def prim_run_host(lib, kind, H, rhs, act=None, reg_rel=0.0, nF=0, bw=0, ex=(), x_in=None, seed=0):
+    """One batch through cave_simt_prim_run on host arrays.  H [B, h] in the entry's layout, rhs [B, p]
+    -> dict(x [B, p], M [B, m], aux [B, 2 p], fail [B])."""
+    k = PRIM_KINDS[kind]
+    rhs = np.ascontiguousarray(rhs, np.float64)
+    B, p = rhs.shape
+    lib.cave_simt_prim_info.restype = C.c_int64
+    info = lambda what: int(lib.cave_simt_prim_info(C.c_int32(k), C.c_int32(what), C.c_int32(p), C.c_int32(nF), C.c_int32(bw)))
+    hs, ws = info(0), info(1)
+    assert hs >= 0, (kind, p, nF, bw)
+    H = np.ascontiguousarray(H, np.float64).reshape(B, -1)
+    assert H.shape[1] == hs, (H.shape, hs)
+    act = np.zeros((B, p), np.uint8) if act is None else np.ascontiguousarray(act, np.uint8)
+    ex = np.ascontiguousarray(ex, np.int32)
+    m = prim_m_entries(kind, p, nF)
+    out = {"x": np.full((B, p), np.nan), "M": np.full((B, m), np.nan), "aux": np.full((B, 2 * p), np.nan),
+           "fail": np.full(B, -7, np.int32)}
+    if x_in is not None:
+        out["x"][...] = x_in
+    wsa = np.full((B, max(ws, 1)), np.nan)
+    a = PrimBatch(B=B, p=p, nF=nF, bw=bw, n_ex=len(ex), reg_rel=reg_rel, H=H.ctypes.data, h_stride=hs,
+                  rhs=rhs.ctypes.data, act=act.ctypes.data, ex=ex.ctypes.data if len(ex) else None, x=out["x"].ctypes.data,
+                  M=out["M"].ctypes.data, m_stride=m, aux=out["aux"].ctypes.data, ws=wsa.ctypes.data, ws_stride=max(ws, 1),
+                  fail=out["fail"].ctypes.data)
+    rc = lib.cave_simt_prim_run(C.c_int32(k), C.byref(a), C.c_uint64(seed))
+    assert rc == 0, (rc, kind, p, nF, bw)
+    return out
 
 
 def store_bandwidth(arrs, B, d):

@@ -1,0 +1,92 @@
+"""ctypes loader of tests/prims/_prims.so: the linear solvers of the Newton loop as gfx950 kernels of their own
+(TEST INFRASTRUCTURE ONLY; tests/prims/prim_entries.h + prims_abi.hip).  Built with the product's HIPCC_FLAGS against
+cave_amd/csrc; torch owns the buffers and the stream.  Nothing under cave_amd/ imports this."""
+
+from __future__ import annotations
+
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_ROOT = os.path.dirname(os.path.dirname(_HERE))
+_SRC = os.path.join(_HERE, "prims_abi.hip")
+_OBJ_DIR = os.path.join(_HERE, "build")
+LIB_PATH = os.path.join(_HERE, "_prims.so")
+# (object name, extra flags): the entries as the product compiles them, and the dense entries once more with the
+# two-columns-per-lane trailing update of cone_dense.h instead of the MFMA one, under the symbol suffix _nomfma
+_UNITS = (("prims", ()), ("prims_nomfma", ("-DCAVE_DENSE_NO_MFMA", "-DCAVE_PRIMS_DENSE_ONLY", "-DCAVE_PRIMS_SUFFIX=_nomfma")))
+
+
+def build(verbose: bool = False) -> str:
+    from concurrent.futures import ThreadPoolExecutor
+
+    from cave_amd import _lib
+
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    deps = [_SRC, os.path.join(_HERE, "prim_entries.h")] + list(_lib._HEADERS)
+    newest = max(os.path.getmtime(p) for p in deps)
+    os.makedirs(_OBJ_DIR, exist_ok=True)
+    objs = [os.path.join(_OBJ_DIR, name + ".o") for name, _ in _UNITS]
+    todo = [(o, fl) for o, (_, fl) in zip(objs, _UNITS) if not os.path.exists(o) or os.path.getmtime(o) < newest]
+    if not todo and os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(o) for o in objs):
+        return LIB_PATH
+
+    def compile_one(job):
+        obj, extra = job
+        cmd = [hipcc, *_lib.HIPCC_FLAGS, "-I" + _lib._CSRC, "-I" + os.path.join(_ROOT, "include"), "-I" + _HERE, *extra,
+               "-c", _SRC, "-o", obj]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.run(cmd, check=True)
+
+    with ThreadPoolExecutor(max_workers=2) as ex:
+        list(ex.map(compile_one, todo))
+    subprocess.run([hipcc, "--offload-arch=gfx950", "-fPIC", "-shared", *objs, "-o", LIB_PATH], check=True)
+    return LIB_PATH
+
+
+class Prims:
+    """run(kind, ...) with the contract of emul_lib.prim_run_host, on cuda:0.  nomfma: the dense entries built with
+    CAVE_DENSE_NO_MFMA (the other entries exist in one form only)."""
+
+    def __init__(self):
+        if not os.path.exists(LIB_PATH):
+            raise ImportError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
+        self.lib = C.CDLL(LIB_PATH)
+        self.lib.cave_prims_info.restype = C.c_int64
+
+    def run(self, kind, H, rhs, act=None, reg_rel=0.0, nF=0, bw=0, ex=(), x_in=None, seed=0, nomfma=False):
+        import torch
+
+        from emul_lib import PRIM_KINDS, PrimBatch, prim_m_entries
+
+        dev = torch.device("cuda:0")
+        k = PRIM_KINDS[kind]
+        rhs = np.ascontiguousarray(rhs, np.float64)
+        B, p = rhs.shape
+        info = lambda what: int(self.lib.cave_prims_info(C.c_int32(k), C.c_int32(what), C.c_int32(p), C.c_int32(nF), C.c_int32(bw)))
+        hs, ws = info(0), max(info(1), 1)
+        assert hs >= 0, (kind, p, nF, bw)
+        H = np.ascontiguousarray(H, np.float64).reshape(B, -1)
+        assert H.shape[1] == hs, (H.shape, hs)
+        m = prim_m_entries(kind, p, nF)
+        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).to(dev)
+        tH, trhs = t(H, np.float64), t(rhs, np.float64)
+        tact = t(np.zeros((B, p), np.uint8) if act is None else act, np.uint8)
+        tex = t(np.asarray(ex if len(ex) else [0], np.int32), np.int32)
+        tx = t(np.full((B, p), np.nan) if x_in is None else x_in, np.float64)
+        tM = torch.full((B, m), float("nan"), dtype=torch.float64, device=dev)
+        taux = torch.full((B, 2 * p), float("nan"), dtype=torch.float64, device=dev)
+        tws = torch.full((B, ws), float("nan"), dtype=torch.float64, device=dev)
+        tfail = torch.full((B,), -7, dtype=torch.int32, device=dev)
+        a = PrimBatch(B=B, p=p, nF=nF, bw=bw, n_ex=len(ex), reg_rel=reg_rel, H=tH.data_ptr(), h_stride=hs,
+                      rhs=trhs.data_ptr(), act=tact.data_ptr(), ex=tex.data_ptr(), x=tx.data_ptr(), M=tM.data_ptr(),
+                      m_stride=m, aux=taux.data_ptr(), ws=tws.data_ptr(), ws_stride=ws, fail=tfail.data_ptr())
+        fn = self.lib.cave_prims_run_nomfma if nomfma else self.lib.cave_prims_run
+        rc = fn(C.c_int32(k), C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        assert rc == 0, (rc, kind, p, nF, bw)
+        torch.cuda.synchronize()
+        return {"x": tx.cpu().numpy(), "M": tM.cpu().numpy(), "aux": taux.cpu().numpy(), "fail": tfail.cpu().numpy()}

@@ -144,10 +144,11 @@ def test_constructor_error_behaviour(monkeypatch):
 
 
 def test_no_oracle_or_emul_in_product_path():
-    """The package must never import the oracle or the serial test build."""
+    """The package must never import the oracle, the serial / emulation test builds or the test-only solver library."""
     pkg = os.path.join(ROOT, "cave_amd")
     for fn in os.listdir(pkg):
         if fn.endswith(".py"):
             src = open(os.path.join(pkg, fn)).read()
             assert "oracle" not in src.replace("no oracle", "") or fn == "__init__.py" and False, fn
             assert "emul" not in src, fn
+            assert "prims_lib" not in src and "_prims.so" not in src, fn   # tests/prims/_prims.so: the solvers alone, test infrastructure too

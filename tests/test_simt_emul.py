@@ -280,6 +280,13 @@ def test_simt_build_is_asan_ubsan_clean():
         "    if S.step_lds_bytes(bt['ctrs'].shape[1], cs.d) > 0:\n"
         "        fs,fa,s3 = S.step_pack(bt['ctrs'], seed=7)\n"
         "        S.step_solve(fs, bt['pred'], 2, m_max=bt['ctrs'].shape[1], flags=1, seed=9)\n"
+        "import linsys_cases as LS\n"   # the linear solvers alone (tests/prims/prim_entries.h): exact-size, poisoned LDS
+        "LS.check_solves(S.prim_run, 'spd_l4', 57, 1e-12, seed=3); LS.check_solves(S.prim_run, 'gjs_tri', 33, 0.0)\n"
+        "LS.check_solves(S.prim_run, 'gj_lower', 64, 1e-6); LS.check_solves(S.prim_run, 'spd_solo', 8, 0.0)\n"
+        "LS.check_gj_partial(S.prim_run, 25, 20, 1e-12); LS.check_tableau(S.prim_run, LS.EXCHANGES[4], 8)\n"
+        "LS.check_dense(S.prim_run, 'dense_w4', 127, 100, 1e-12, seed=4); LS.check_dense(S.prim_run, 'dense_w2', 5, 0, 0.0)\n"
+        "for kd, bw, p in (('bandw1', 13, 97), ('bandw2', 33, 129), ('band_hot_l4', 12, 65), ('band_cold_l4', 2, 65), ('band_hot_w1', 34, 36)):\n"
+        "    LS.check_solves(S.prim_run, kd, p, 1e-12, bw=bw, seed=5)\n"
         "print('asan-ok', S.path_counters())\n" % (ROOT, os.path.join(ROOT, "tests"), so, os.path.join(ROOT, "tests")))
     env = dict(os.environ, LD_PRELOAD=libasan, ASAN_OPTIONS="detect_leaks=0:detect_stack_use_after_return=0")
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=900)
