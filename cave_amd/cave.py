@@ -23,7 +23,8 @@ import torch
 from . import _lib
 from .abcmodule import EPO, optModule, sense_sign
 from .dataset import PackedBatch
-from .qpsolver import PreparedCones, _step_qualifies, cone_op_dense, cone_op_prepared, cone_op_sparse, prepare_dense
+from .qpsolver import (PreparedCones, _step_qualifies, _step_qualifies_sparse, cone_op_dense, cone_op_prepared, cone_op_sparse,
+                       prepare_cones, prepare_dense, prepare_sparse)
 from .sparse import SparseCones
 from .warm import DEFAULT_ENTRIES, WarmCache
 
@@ -156,10 +157,17 @@ class _ConeLossFunction(torch.autograd.Function):
 
             if qpsolver._step_ok.get(tight_ctrs.shape[1:]) is False:
                 # prepared before a verdict said that this shape holds cones the step kernel does not take (_examine):
-                # the dense tensor it keeps goes down the general path, status-checked until a tier has settled
+                # the batch it keeps (tensor or SparseCones) goes down the general path, status-checked until a tier has settled
                 tight_ctrs = tight_ctrs.ctrs
-        if warm is not None and (mode not in _WARM_MODES or isinstance(tight_ctrs, SparseCones)):
-            warm = None  # (a batch on the sparse wire format runs cold)
+        if warm is not None and mode not in _WARM_MODES:
+            warm = None
+        if warm is not None and isinstance(tight_ctrs, SparseCones):
+            # warm start on a plain sparse batch: the split form of the fused step (pack-only launch, then the warm solve);
+            # a shape the step does not take runs cold on today's route
+            if _step_qualifies_sparse(tight_ctrs) and tight_ctrs.device == warm.device:
+                tight_ctrs = prepare_sparse(tight_ctrs)
+            else:
+                warm = None
         if warm is not None and not isinstance(tight_ctrs, (PackedBatch, PreparedCones)) and _warm_dense_ok(tight_ctrs, kwargs) \
                 and tight_ctrs.device == warm.device:
             # warm start on a plain dense batch: the split form of the fused step (pack-only launch, then solve)
@@ -191,6 +199,8 @@ class _ConeLossFunction(torch.autograd.Function):
         if lazy:
             if isinstance(tight_ctrs, SparseCones):
                 _defer_check(o["status"], "solver='hip' (lazy check, sparse cones)", (tight_ctrs.m_max, tight_ctrs.d))
+            elif isinstance(tight_ctrs, PreparedCones) and tight_ctrs.sparse:
+                _defer_check(o["status"], "solver='hip' (lazy check, sparse cones)", tight_ctrs.shape[1:], prepared=True)
             else:
                 shape = None if isinstance(tight_ctrs, PackedBatch) else (int(tight_ctrs.shape[1]), int(tight_ctrs.shape[2]))
                 _defer_check(o["status"], "solver='hip' (lazy check)", shape, prepared=isinstance(tight_ctrs, PreparedCones))
@@ -225,7 +235,8 @@ class abstractConeAlignedCosine(optModule):
     def forward(self, pred_cost: torch.Tensor, tight_ctrs: torch.Tensor) -> torch.Tensor:
         """`tight_ctrs`: the reference's dense (B, m_max, d) tensor, a PackedBatch (store + ids), a PreparedCones, or a
         cave_amd.sparse.SparseCones (the sparse wire format: same loss and gradient as the dense tensor it stands for;
-        ``check`` as for a PackedBatch; ``solver_kwargs["warm_start"]`` does not apply to it -- such a batch runs cold)."""
+        ``check`` as for a PackedBatch; under ``solver_kwargs["warm_start"]`` a batch of a shape the fused step takes is
+        packed by a launch of its own and solved warm, like a plain dense batch)."""
         sign = sense_sign(self.optmodel.modelSense)  # ValueError on a bad sense, src/cave.py:62-67
         kwargs = self._solver_kwargs_for_call()
         mode = self._mode()
@@ -238,10 +249,13 @@ class abstractConeAlignedCosine(optModule):
         """The module's multiplier cache (solver_kwargs={"warm_start": ...}) when this call can use it -- a projection
         mode on a prepared batch or a plain dense batch the fused step takes; None otherwise (a PackedBatch warm-starts
         through its store).  Created on the device of the first call that can use it."""
-        if mode not in _WARM_MODES or isinstance(tight_ctrs, (PackedBatch, SparseCones)):
+        if mode not in _WARM_MODES or isinstance(tight_ctrs, PackedBatch):
             return None
-        if not isinstance(tight_ctrs, PreparedCones) and not (isinstance(tight_ctrs, torch.Tensor) and
-                                                              _warm_dense_ok(tight_ctrs, _op_kwargs(kwargs))):
+        if isinstance(tight_ctrs, SparseCones):
+            if not _step_qualifies_sparse(tight_ctrs):
+                return None
+        elif not isinstance(tight_ctrs, PreparedCones) and not (isinstance(tight_ctrs, torch.Tensor) and
+                                                                _warm_dense_ok(tight_ctrs, _op_kwargs(kwargs))):
             return None
         cache = getattr(self, "_warm", None)
         if cache is None:
@@ -258,10 +272,11 @@ class abstractConeAlignedCosine(optModule):
         return 0.0
 
     @staticmethod
-    def prepare(tight_ctrs: torch.Tensor, following: "torch.Tensor | None" = None):
+    def prepare(tight_ctrs, following=None):
         """Run the prediction-independent half of the forward pass (streaming the dense cones and building the
-        reduced cones) for a batch now; pass the result in place of `tight_ctrs`: `loss_fn(cp, prep)`.  With
-        `following` (the dense cones of the batch after it -- the DataLoader has collated them already) that batch's
+        reduced cones) for a batch now; pass the result in place of `tight_ctrs`: `loss_fn(cp, prep)`.  Both arguments
+        may be dense tensors or SparseCones (on the device), in any combination.  With
+        `following` (the cones of the batch after it -- the DataLoader has collated them already) that batch's
         half rides in the launch of this batch's loss call, beside its solve, and `prep.next` is what to pass for it:
 
             prep = loss_fn.prepare(bctr_0, bctr_1)
@@ -269,7 +284,7 @@ class abstractConeAlignedCosine(optModule):
 
         (`cave_amd.dataset.prefetch(loader)` does this wiring around a DataLoader.)  Returns the tensor itself when
         the shape does not qualify."""
-        prep = prepare_dense(tight_ctrs)
+        prep = prepare_cones(tight_ctrs)
         if following is not None and isinstance(prep, PreparedCones):
             prep.then(following)
         return prep
@@ -279,6 +294,8 @@ class abstractConeAlignedCosine(optModule):
 
     def _get_projection(self, signed_cost: torch.Tensor, tight_ctrs: torch.Tensor) -> torch.Tensor:
         """The constant target for an already sense-flipped cost (src/cave.py:121-129,197-219)."""
+        if isinstance(tight_ctrs, PreparedCones):
+            tight_ctrs = tight_ctrs.ctrs  # the batch it was prepared from (the target needs no fused step)
         with torch.no_grad():
             if isinstance(tight_ctrs, PackedBatch):
                 o = tight_ctrs.store.cone_op(tight_ctrs.ids, signed_cost, self._mode(), 1.0, self._inner_ratio(),

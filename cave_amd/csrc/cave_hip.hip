@@ -464,6 +464,74 @@ int32_t cave_hip_cone_step_warm(const cave_lite_store* solve, const int64_t* ids
                         iters, next_ctrs, B_next, m_max, d, next, pack_status, warm, keys, warm_hit, cu_tickets, stream);
 }
 
+// the fused step with the NEXT batch on the sparse wire format (kernels.h cone_step_sparse_kernel): the solve half and
+// its arguments are those of cave_hip_cone_step_warm, the pack half reads `next_cones`
+int32_t cave_hip_cone_step_sparse(const cave_lite_store* solve, const int64_t* ids, const float* pred, int64_t B, int32_t mode,
+                                  float sign, float inner_ratio, int32_t max_iter, int32_t flags, float* proj, float* rnorm,
+                                  float* target, float* loss, float* grad, int32_t* status, int32_t* iters,
+                                  const cave_sparse_cones* next_cones, const cave_lite_store* next, int32_t* pack_status,
+                                  const cave_warm_cache* warm, const int64_t* keys, uint8_t* warm_hit, uint32_t* cu_tickets,
+                                  void* stream) {
+  if (!next_cones || next_cones->B == 0) {
+    // solve only: the dense entry point's launch (the same kernel, the same bits); d is the store's
+    if (B > 0 && !solve) return fail(CAVE_E_INVALID, "cone_step_sparse: solve store is null");
+    return cone_step_impl(solve, ids, pred, B, mode, sign, inner_ratio, max_iter, flags, proj, rnorm, target, loss, grad, status,
+                          iters, nullptr, 0, 0, solve ? solve->d : 1, nullptr, nullptr, warm, keys, warm_hit, cu_tickets, stream);
+  }
+  if (warm) {
+    const int64_t n = warm->n_entries;
+    if (n <= 0 || n >= (int64_t)1 << 40 || (n & (n - 1)) != 0)
+      return fail(CAVE_E_INVALID, "cone_step_sparse: n_entries must be a power of two");
+    if (!warm->key || !warm->theta) return fail(CAVE_E_INVALID, "cone_step_sparse: null key / theta array");
+    if (((uintptr_t)warm->theta & 15u) != 0) return fail(CAVE_E_INVALID, "cone_step_sparse: theta must be 16-byte aligned");
+  }
+  int32_t rc = check_sparse("cone_step_sparse", next_cones);
+  if (rc != CAVE_OK) return rc;
+  const int64_t B_next = next_cones->B, m_max = next_cones->m_max, d = next_cones->d;
+  if (B < 0 || B + B_next >= (int64_t)1 << 31) return fail(CAVE_E_INVALID, "cone_step_sparse: bad batch sizes");
+  if (!cu_tickets) return fail(CAVE_E_INVALID, "cone_step_sparse: cu_tickets is null");
+  int32_t cap = 0, lds = 0;
+  if (m_max <= 0 || step_limits(m_max, d, cap, lds) != CAVE_OK)
+    return fail(CAVE_E_INVALID, "cone_step_sparse: shape does not qualify (cave_hip_step_lds_bytes)");
+  if (!next) return fail(CAVE_E_INVALID, "cone_step_sparse: next store is null");
+  if (next->d != d || (B > 0 && solve && solve->d != d))
+    return fail(CAVE_E_INVALID, "cone_step_sparse: d of the batch differs from the store's d");
+  if (!lite_store_ok(next, B_next, d)) return fail(CAVE_E_INVALID, "cone_step_sparse: bad next store (size, d, null or unaligned array)");
+  StepSparseParams P;
+  memset(&P, 0, sizeof(P));
+  if (B > 0) {
+    if (mode < CAVE_MODE_PROJECT || mode > CAVE_MODE_AVG) return fail(CAVE_E_INVALID, "cone_step_sparse: bad mode (PROJECT .. AVG)");
+    if (!pred && mode != CAVE_MODE_AVG) return fail(CAVE_E_INVALID, "cone_step_sparse: pred is null");
+    if (!lite_store_ok(solve, ids ? 1 : B, d)) return fail(CAVE_E_INVALID, "cone_step_sparse: bad solve store (size, d, null or unaligned array)");
+    if (next->hdr == solve->hdr) return fail(CAVE_E_INVALID, "cone_step_sparse: solve and next must be different stores");
+    P.S.store = *solve; P.S.ids = ids; P.S.pred = pred; P.S.B = B; P.S.mode = mode; P.S.sign = sign; P.S.inner_ratio = inner_ratio;
+    P.S.max_iter = max_iter > 0 ? max_iter : 100;
+    P.S.flags = flags;
+    P.S.o = OutPtrs{proj, rnorm, target, loss, grad, status, iters};
+  }
+  P.Q.ent_off = next_cones->ent_off; P.Q.key = next_cones->key; P.Q.val = next_cones->val;
+  P.Q.B = B_next; P.Q.m = (int32_t)m_max; P.Q.d = (int32_t)d; P.Q.nnz_cap = (uint32_t)cap;
+  P.Q.store = *next; P.Q.status = pack_status; P.Q.lite_pmax = lite_pmax_table((int)d);
+  P.lds_bytes = (uint32_t)lds;
+  P.tickets = cu_tickets;
+  if (warm && B > 0) {  // (a pack-only launch has nothing to warm: the cold kernel)
+    StepSparseParamsWarm PW;
+    memset(&PW, 0, sizeof(PW));
+    static_cast<StepSparseParams&>(PW) = P;
+    PW.W.key = warm->key; PW.W.theta = warm->theta; PW.W.n = warm->n_entries; PW.W.keys = keys; PW.W.hit = warm_hit;
+    PW.W.lds_extra = step_warm_lds_extra((uint32_t)lds, true);
+    PW.lds_bytes += PW.W.lds_extra;
+    hipError_t e = launch_step_sparse_warm((unsigned)(B + B_next), PW.lds_bytes, (hipStream_t)stream, PW);
+    if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch cone_step_sparse_kernel (warm)", e);
+    return CAVE_OK;
+  }
+  hipError_t e = warm_hit && B > 0 ? hipMemsetAsync(warm_hit, 0, (size_t)B, (hipStream_t)stream) : hipSuccess;
+  if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "cone_step_sparse: warm_hit", e);
+  e = launch_step_sparse((unsigned)(B + B_next), (uint32_t)lds, (hipStream_t)stream, P);
+  if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch cone_step_sparse_kernel", e);
+  return CAVE_OK;
+}
+
 int32_t cave_hip_lite_from_packed(const cave_cone_store* src, const cave_lite_store* dst, int32_t* status, void* stream) {
   if (!src || !dst) return fail(CAVE_E_INVALID, "lite_from_packed: null store");
   if (src->n == 0) return CAVE_OK;

@@ -152,14 +152,17 @@ typedef float sparse_f32x4 __attribute__((vector_size(16), may_alias));
 // does not fit, the same launch limits on both routes).  An entry that breaks the contract is not stored and not
 // counted; the instance reports ST_BAD_INPUT.  Each entry's predecessor is read from memory (same or previous cache
 // line), so no lane waits for another.
-template <class C, bool LARGE = false>
+// DEEP (the step kernel's sparse pack half, cone_step.h): no dump slots either -- the stores here are predicated in every
+// form, so the slots are never written -- which makes the reservations those of scan_and_build<C, false, true>: the
+// arena step_limits sizes for the dense pack half.
+template <class C, bool LARGE = false, bool DEEP = false>
 CAVE_HD int32_t load_sparse_and_build(C& c, Arena& ar, ConeBuild& cb, const uint32_t* key, const float* val, int64_t nent,
                                       int m, int d, uint32_t cap) {
   constexpr uint32_t NT = (uint32_t)C::NT;
   cb.d = d;
   cb.m = m;
   if (m > 0xffff || d > 0xffff) return ST_TOO_LARGE;
-  const uint32_t dump_slots = LARGE ? 0u : NT;
+  const uint32_t dump_slots = (LARGE || DEEP) ? 0u : NT;
   cb.erc = ar.get_top<uint32_t>(cap + dump_slots);
   cb.eall = ar.get_top<float>(cap + dump_slots);
   cb.rptr = ar.get_top<uint32_t>((uint32_t)m + 1u);

@@ -47,6 +47,19 @@ struct StepPackParams {
   uint64_t lite_pmax;   // lite_pmax_table(d): most reduced rows a cone with nI = 1 .. 8 bound rows may have (byte nI - 1)
 };
 
+// the pack half from the sparse wire format (cave_sparse_cones): a kernel argument of its own (cone_step_sparse_kernel)
+struct StepSparsePackParams {
+  const int64_t* ent_off;
+  const uint32_t* key;
+  const float* val;
+  int64_t B;
+  int32_t m, d;
+  uint32_t nnz_cap;
+  cave_lite_store store;
+  int32_t* status;
+  uint64_t lite_pmax;
+};
+
 // Multiplier cache of the warm solve half (cave_warm_cache, include/cave_hip.h): n entries of one 64-bit key and 32
 // float multipliers each, grouped in sets of min(4, n) ways.  A key hashes to one set; lanes 0..ways-1 load the set's
 // keys (ONE load) and lanes 0..31 the multipliers of all its ways beside them, so a hit costs no second round trip.
@@ -73,6 +86,17 @@ struct StepParams {
 };
 // the warm variant's kernel argument (cone_step_kernel<CP, true>): the cold one keeps its own as it was
 struct StepParamsWarm : StepParams {
+  StepWarm W;
+};
+// the same pair for a NEXT batch on the sparse wire format (cone_step_sparse_kernel): the solve half is the dense
+// kernels' (it reads only the lite store), the pack half copies the coordinate list instead of scanning a dense block
+struct StepSparseParams {
+  StepSolveParams S;
+  StepSparsePackParams Q;
+  uint32_t lds_bytes;
+  uint32_t* tickets;
+};
+struct StepSparseParamsWarm : StepSparseParams {
   StepWarm W;
 };
 
@@ -271,6 +295,39 @@ CAVE_HD void run_pack_lite_instance(C& c, unsigned char* smem, uint32_t lds_byte
   ConeBuild cb;
   CAVE_T0();
   int32_t st = scan_and_build<C, false, true>(c, ar, cb, P.ctrs + b * (int64_t)m * d, m, d, P.nnz_cap);
+  CAVE_ACC(0);
+  const cave_lite_store& S = P.store;
+  float* avg = (st == ST_OK) ? ar.get<float>(d) : nullptr;
+  if (st == ST_OK && ar.ovf) st = ST_TOO_LARGE;
+  if (st == ST_OK) {
+    compute_avg(c, cb, avg);
+    ar.release_top();  // build-phase temporaries are dead now
+    const SolveView v = view_of(cb);
+    if (write_lite_slot(c, ar, v, avg, cb.nnzM, S, b, P.lite_pmax) != 1) st = ST_TOO_LARGE;
+  } else if (c.tid() == 0) {
+    int32_t* h = S.hdr + b * kLiteHdr;
+    h[0] = -1;
+    for (int i = 1; i < kLiteHdr; ++i) h[i] = 0;
+  }
+  CAVE_ACC(1);
+  if (c.tid() == 0 && P.status) P.status[b] = st;
+}
+
+// Twin of run_pack_lite_instance for one instance of the sparse wire format: load_sparse_and_build in its DEEP form
+// (the reservations of scan_and_build<C, false, true>: the same arena from the same step_limits LDS and nnz_cap) is
+// the producer, everything after it is the same text.  From the same non-zeros build_cone therefore sees the same
+// input in the same arena, and the slot holds the same bits and the same TOO_LARGE verdicts as on the dense route.
+// A twin and not a shared tail: the code objects of the dense step kernels stay as they are.  A
+// contract-breaking entry: ST_BAD_INPUT in `status`, slot state -1.
+template <class C>
+CAVE_HD void run_pack_sparse_lite_instance(C& c, unsigned char* smem, uint32_t lds_bytes, const StepSparsePackParams& P, int64_t b) {
+  const int d = P.d, m = P.m;
+  Arena ar;
+  ar.init(smem + C::SCRATCH_BYTES, lds_bytes - C::SCRATCH_BYTES);
+  ConeBuild cb;
+  CAVE_T0();
+  const int64_t e0 = P.ent_off[b];
+  int32_t st = load_sparse_and_build<C, false, true>(c, ar, cb, P.key + e0, P.val + e0, P.ent_off[b + 1] - e0, m, d, P.nnz_cap);
   CAVE_ACC(0);
   const cave_lite_store& S = P.store;
   float* avg = (st == ST_OK) ? ar.get<float>(d) : nullptr;

@@ -297,6 +297,49 @@ __global__ __launch_bounds__(CP::NT, 2) void cone_step_kernel(typename StepArg<W
 #endif
 }
 
+// ---- the fused step kernel for a NEXT batch on the sparse wire format (cone_step.h run_pack_sparse_lite_instance):
+// blocks [0, S.B) are the solve half of cone_step_kernel word for word (it reads only the lite store, whichever route
+// packed it); blocks [S.B, S.B + Q.B) copy the coordinate list of instance b - S.B and build its lite slot, on the same
+// two-wave workgroups, in the same arena.  A kernel and a kernel argument of its own: cone_step_kernel's code objects
+// stay as they are.
+template <bool WARM> struct StepSparseArg { using type = StepSparseParams; };
+template <> struct StepSparseArg<true> { using type = StepSparseParamsWarm; };
+template <class CP, bool WARM = false>
+__global__ __launch_bounds__(CP::NT, 2) void cone_step_sparse_kernel(typename StepSparseArg<WARM>::type P) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int64_t b = blockIdx.x;
+  uint32_t lds_bytes = P.lds_bytes;
+  StepWarm W{};
+  if constexpr (WARM) {
+    W = P.W;
+    lds_bytes -= W.lds_extra;
+  }
+  if (b < P.S.B) {
+    uint32_t claim = 0;
+    const int sel = step_elect_wave<CP::NWAVES>(smem, P.tickets, claim);
+    if ((int)(threadIdx.x >> 6) != sel) return;
+    if (CAVE_STEP_SOLVE_PRIO) __builtin_amdgcn_s_setprio(CAVE_STEP_SOLVE_PRIO);
+    SoloCtx<32, 4> sc;
+    sc.lane = (int)(threadIdx.x & 63u);
+#ifdef CAVE_STAMPS
+    unsigned long long stamps[32];
+    for (int i = 0; i < 32; ++i) stamps[i] = 0;
+    sc.st = stamps;
+#endif
+    run_lite_instance<SoloCtx<32, 4>, WARM>(sc, smem + kStepElectBytes, lds_bytes - kStepElectBytes, P.S, b, W);
+    if (sc.lane == 0) step_release(P.tickets, claim);
+    return;
+  }
+  if (CAVE_STEP_PACK_PRIO) __builtin_amdgcn_s_setprio(CAVE_STEP_PACK_PRIO);
+  CP c;
+  c.init(smem);
+  const int64_t q = b - P.S.B;
+#ifdef CAVE_STAMPS
+  for (int i = 0; i < 32; ++i) c.st[i] = 0;
+#endif
+  if (q < P.Q.B) run_pack_sparse_lite_instance(c, smem, lds_bytes, P.Q, q);
+}
+
 // packed cone store -> lite store, one workgroup per instance (run once per store: cones are static)
 template <class C>
 __global__ CAVE_BOUNDS(C) void lite_from_packed_kernel(LiteFromPackedParams P) {
@@ -337,6 +380,8 @@ CAVE_DECL_LAUNCH(launch_pack_sparse_w8, SparsePackParams);
 CAVE_DECL_LAUNCH_LARGE(launch_pack_sparse_large, SparsePackParams);
 CAVE_DECL_LAUNCH(launch_step, StepParams);
 CAVE_DECL_LAUNCH(launch_step_warm, StepParamsWarm);
+CAVE_DECL_LAUNCH(launch_step_sparse, StepSparseParams);
+CAVE_DECL_LAUNCH(launch_step_sparse_warm, StepSparseParamsWarm);
 CAVE_DECL_LAUNCH(launch_lite_from_packed, LiteFromPackedParams);
 
 template <class K>

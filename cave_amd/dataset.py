@@ -533,7 +533,8 @@ def collate_ids(batch):
 
 
 def prefetch(loader, slot: int = -1, device=None):
-    """Wrap a DataLoader whose batches carry the dense `tight_ctrs` in field `slot` (the reference's collate_fn puts
+    """Wrap a DataLoader whose batches carry the dense `tight_ctrs` -- or, from a loader built with
+    cave_amd.sparse.collate_sparse, a SparseCones -- in field `slot` (the reference's collate_fn puts
     it last: src/dataset.py:133-144) so that the loop body of code_sample.py:48-60 stays as it is,
 
         for data in prefetch(loader):
@@ -545,7 +546,7 @@ def prefetch(loader, slot: int = -1, device=None):
     of batch i packs batch i+1 in the same launch (qpsolver.cone_op_prepared).  One batch of look-ahead: the generator
     pulls batch i+1 from the loader before it yields batch i.  Cones are moved to `device` (default: the current HIP
     device) here; shapes the fused form does not take pass through as tensors."""
-    from .qpsolver import PreparedCones, prepare_dense
+    from .qpsolver import PreparedCones, prepare_cones
 
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
 
@@ -557,7 +558,7 @@ def prefetch(loader, slot: int = -1, device=None):
         cur = next(it)
     except StopIteration:
         return
-    cur_cones = prepare_dense(cones_of(cur))
+    cur_cones = prepare_cones(cones_of(cur))
     while True:
         try:
             nxt = next(it)
@@ -568,11 +569,14 @@ def prefetch(loader, slot: int = -1, device=None):
             cur_cones.then(nxt_dense)
         out = list(cur)
         out[slot] = cur_cones
-        yield type(cur)(out) if isinstance(cur, (tuple, list)) else out
+        if isinstance(cur, tuple) and hasattr(cur, "_fields"):
+            yield type(cur)(*out)  # a namedtuple batch keeps its type
+        else:
+            yield type(cur)(out) if isinstance(cur, (tuple, list)) else out
         if nxt is None:
             return
         if isinstance(cur_cones, PreparedCones) and cur_cones.next is not None:
             nxt_cones = cur_cones.next          # packed by the loss call of the batch just yielded
         else:                                   # (no loss call happened on it, or the shape does not qualify)
-            nxt_cones = prepare_dense(nxt_dense)
+            nxt_cones = prepare_cones(nxt_dense)
         cur, cur_cones = nxt, nxt_cones

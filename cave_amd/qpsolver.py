@@ -23,7 +23,7 @@ from ._lib import (MODE_AVG, MODE_EXACT, MODE_HEURISTIC, MODE_INNER, MODE_PROJEC
                    ST_NOT_CONVERGED, ST_OK, ST_TOO_LARGE)
 
 __all__ = ["project_hip", "average_ctrs_hip", "cone_op_dense", "HipSolverError", "PreparedCones", "prepare_dense",
-           "cone_op_prepared", "step_lds_bytes", "cone_op_sparse", "project_hip_sparse"]
+           "prepare_sparse", "prepare_cones", "cone_op_prepared", "step_lds_bytes", "cone_op_sparse", "project_hip_sparse"]
 
 
 class HipSolverError(RuntimeError):
@@ -232,23 +232,26 @@ def _take_store(dev, B: int, d: int, avoid=None) -> _LiteSlots:
 
 
 class PreparedCones:
-    """A dense (B, m_max, d) batch whose reduced cones sit in a transient lite store (packed by an earlier launch on
-    the same stream).  Usable in place of `tight_ctrs` in a loss call.  `then(next_ctrs)` attaches the batch that
-    follows: the loss call then packs it in the same launch and leaves its PreparedCones in `.next`.  Keeps the dense
-    tensor alive for the fallback of a batch the lite form does not take -- or whose store has been handed out again
-    in the meantime (`gen` no longer matches: more prepared batches held than the pool has stores)."""
+    """A batch -- a dense (B, m_max, d) tensor or a SparseCones -- whose reduced cones sit in a transient lite store
+    (packed by an earlier launch on the same stream).  Usable in place of `tight_ctrs` in a loss call.
+    `then(next_cones)` attaches the batch that follows, a tensor or a SparseCones (its kind chooses the kernel; the
+    solve half does not care which route packed its store, so a chain may alternate): the loss call then packs it in
+    the same launch and leaves its PreparedCones in `.next`.  Keeps the batch itself (`ctrs`) alive for the fallback of
+    a batch the lite form does not take -- or whose store has been handed out again in the meantime (`gen` no longer
+    matches: more prepared batches held than the pool has stores)."""
 
-    def __init__(self, ctrs: torch.Tensor, store: _LiteSlots, gen: int):
+    def __init__(self, ctrs, store: _LiteSlots, gen: int):
         self.ctrs, self.store, self.gen = ctrs, store, gen
-        self.shape = tuple(ctrs.shape)
-        self.follow = None   # dense tensor of the batch after this one (consumed by the first solve)
-        self.next = None     # what to pass for that batch: a PreparedCones, or the tensor itself
+        self.sparse = not isinstance(ctrs, torch.Tensor)
+        self.shape = (len(ctrs), ctrs.m_max, ctrs.d) if self.sparse else tuple(ctrs.shape)
+        self.follow = None   # the batch after this one (consumed by the first solve)
+        self.next = None     # what to pass for that batch: a PreparedCones, or the batch itself
 
     def stale(self) -> bool:
         return self.gen != self.store.gen
 
-    def then(self, next_ctrs: "torch.Tensor | None") -> "PreparedCones":
-        self.follow, self.next = next_ctrs, None
+    def then(self, next_cones) -> "PreparedCones":
+        self.follow, self.next = next_cones, None
         return self
 
     # a training loop moves every field of a batch to the device (code_sample.py:50): nothing to move here
@@ -268,6 +271,35 @@ def _step_qualifies(t) -> bool:
         return False
     B, m, d = t.shape
     return 0 < m and d <= SPLIT_MAX_D and 0 < B <= STEP_MAX_B and _step_ok.get((m, d)) is not False and step_lds_bytes(m, d) > 0
+
+
+def _step_qualifies_sparse(x) -> bool:
+    """_step_qualifies for a SparseCones: the same rules on (B, m_max, d) and the same verdicts (`_step_ok` is shared
+    with the dense route: from the same non-zeros the two pack halves refuse the same cones)."""
+    from .sparse import SparseCones
+
+    if not (isinstance(x, SparseCones) and x.is_cuda):
+        return False
+    B, m, d = len(x), x.m_max, x.d
+    return 0 < m <= 32767 and d <= SPLIT_MAX_D and 0 < B <= STEP_MAX_B and _step_ok.get((m, d)) is not False and step_lds_bytes(m, d) > 0
+
+
+def _launch_step_sparse(solve, pred, B, mode, sign, inner_ratio, max_iter, out, status, iters, nxt_cones, nxt_store,
+                        zero_failed=False, warm=None, keys=None):
+    """_launch_step with the next batch on the sparse wire format (cave_hip_cone_step_sparse)."""
+    lib = _lib.load()
+    dev = nxt_cones.device
+    hit = None
+    if warm is not None and B > 0:
+        hit = out["warm_hit"] = torch.empty(B, dtype=torch.uint8, device=dev)
+    rc = lib.cave_hip_cone_step_sparse(
+        solve.ref if solve is not None else None, None, _lib.ptr(pred), B, int(mode), float(sign), float(inner_ratio),
+        int(max_iter), 1 if zero_failed else 0,
+        _lib.ptr(out.get("proj")), _lib.ptr(out.get("rnorm")), _lib.ptr(out.get("target")), _lib.ptr(out.get("loss")),
+        _lib.ptr(out.get("grad")), _lib.ptr(status), _lib.ptr(iters),
+        nxt_cones.c_ref(), nxt_store.ref, _lib.ptr(nxt_store.pack_status),
+        warm.ref if hit is not None else None, _lib.ptr(keys), _lib.ptr(hit), _lib.ptr(_tickets_for(dev)), _lib.current_stream())
+    _lib.check(rc, "cave_hip_cone_step_sparse")
 
 
 def _launch_step(solve, pred, B, mode, sign, inner_ratio, max_iter, out, status, iters, nxt_ctrs, nxt_store, ids=None,
@@ -309,23 +341,49 @@ def prepare_dense(tight_ctrs: torch.Tensor) -> "PreparedCones | torch.Tensor":
     return PreparedCones(ctrs, ss, ss.gen)
 
 
+def prepare_sparse(cones) -> "PreparedCones":
+    """prepare_dense for a batch on the sparse wire format: a pack-only launch of cave_hip_cone_step_sparse into a pooled
+    lite store.  Returns the batch itself (on the device) when the shape does not qualify."""
+    _lib.load()
+    x = cones if cones.is_cuda else cones.cuda()
+    if not _step_qualifies_sparse(x):
+        return x
+    dev = x.device
+    with torch.cuda.device(dev):
+        ss = _take_store(dev, len(x), x.d)
+        _launch_step_sparse(None, None, 0, MODE_PROJECT, 1.0, 0.0, 0, {}, None, None, x, ss)
+    return PreparedCones(x, ss, ss.gen)
+
+
+def prepare_cones(x):
+    """prepare_dense for a tensor, prepare_sparse for a SparseCones."""
+    return prepare_dense(x) if isinstance(x, torch.Tensor) else prepare_sparse(x)
+
+
 def cone_op_prepared(prep: PreparedCones, pred_cost: torch.Tensor, mode: int, sign: float = 1.0, inner_ratio: float = 0.2, *,
                      max_iter: int = 0, check: bool = True, zero_failed: bool = False,
                      outputs: tuple[str, ...] = ("proj", "rnorm"), warm=None, keys=None) -> dict[str, torch.Tensor]:
     """The solve stage for a prepared batch (same outputs as cone_op_dense) and, in the same launch, the pack stage of
-    the batch attached with `prep.then(...)`, whose PreparedCones is left in `prep.next`.  A batch with a cone the lite
-    form does not take falls back to cone_op_dense on the dense tensor (checked calls only; unchecked calls report
-    CAVE_ST_TOO_LARGE in `status`).  `warm` (cave_amd.warm.WarmCache on this device) / `keys` ([B] int64 or None:
+    the batch attached with `prep.then(...)` -- a dense tensor (cave_hip_cone_step) or a SparseCones
+    (cave_hip_cone_step_sparse) -- whose PreparedCones is left in `prep.next`.  A batch with a cone the lite
+    form does not take falls back to the general operator of its own wire format, cone_op_dense or cone_op_sparse
+    (checked calls only; unchecked calls report CAVE_ST_TOO_LARGE in `status`); an instance the sparse loader rejected
+    reports CAVE_ST_BAD_INPUT.  `warm` (cave_amd.warm.WarmCache on this device) / `keys` ([B] int64 or None:
     keyed by cone content): warm start from the cache, out["warm_hit"] says where it hit (the fallbacks run cold)."""
     _lib.load()
     B, m, d = prep.shape
     dev = prep.ctrs.device
+
+    def general(chk):  # the batch itself through the general operator of its wire format
+        op = cone_op_sparse if prep.sparse else cone_op_dense
+        return op(prep.ctrs, pred_cost, mode, sign, inner_ratio, max_iter=max_iter, check=chk, outputs=outputs)
+
     follow, prep.follow = prep.follow, None
     if prep.stale() or mode == _lib.MODE_INNER_IPM:
-        # its store now holds a later batch (or the mode is not one of the step kernel's): solve from the dense tensor
+        # its store now holds a later batch (or the mode is not one of the step kernel's): solve from the batch itself
         if follow is not None:
-            prep.next = prepare_dense(follow)
-        return cone_op_dense(prep.ctrs, pred_cost, mode, sign, inner_ratio, max_iter=max_iter, check=check, outputs=outputs)
+            prep.next = prepare_cones(follow)
+        return general(check)
     pred = _as_device(pred_cost, dev)
     if pred.shape != (B, d):
         raise ValueError(f"pred_cost must have shape ({B}, {d}), got {tuple(pred.shape)}")
@@ -337,25 +395,36 @@ def cone_op_prepared(prep: PreparedCones, pred_cost: torch.Tensor, mode: int, si
         iters = torch.empty(B, dtype=torch.int32, device=dev)
         out["status"], out["iters"] = status, iters
         nctrs = nstore = None
+        nsparse = False
         if follow is not None:
             if _step_qualifies(follow):
                 nctrs = _as_device(follow, dev)
                 nstore = _take_store(dev, int(nctrs.shape[0]), int(nctrs.shape[2]), avoid=prep.store)
                 prep.next = PreparedCones(nctrs, nstore, nstore.gen)
+            elif _step_qualifies_sparse(follow) and follow.device == dev:
+                nctrs, nsparse = follow, True
+                nstore = _take_store(dev, len(nctrs), nctrs.d, avoid=prep.store)
+                prep.next = PreparedCones(nctrs, nstore, nstore.gen)
             else:
                 prep.next = follow
         if keys is not None and (keys.device != dev or keys.dtype != torch.int64 or not keys.is_contiguous()):
             keys = keys.to(device=dev, dtype=torch.int64).contiguous()
-        _launch_step(prep.store, pred, B, mode, sign, inner_ratio, max_iter, out, status, iters, nctrs, nstore,
-                     zero_failed=zero_failed, warm=warm, keys=keys)
+        # the pack status of THIS batch (its store may be packed again by a later launch: keep the verdict now, in stream order)
+        bad = (prep.store.pack_status == ST_BAD_INPUT) if prep.sparse else None
+        launch = _launch_step_sparse if nsparse else _launch_step
+        launch(prep.store, pred, B, mode, sign, inner_ratio, max_iter, out, status, iters, nctrs, nstore,
+               zero_failed=zero_failed, warm=warm, keys=keys)
+        if bad is not None:
+            # an instance the sparse loader rejected left slot state -1, which the solve reports as TOO_LARGE: its own
+            # verdict is the loader's (as cone_op_sparse)
+            status = out["status"] = torch.where(bad, torch.full_like(status, ST_BAD_INPUT), status)
         if zero_failed:
             out["zero_failed"] = True  # (the kernel wrote loss 0 / gradient 0 for instances whose status is not OK)
         if check:
             if bool((status == ST_TOO_LARGE).any()):
                 _step_ok[(m, d)] = False
-                return cone_op_dense(prep.ctrs, pred_cost, mode, sign, inner_ratio, max_iter=max_iter, check=True,
-                                     outputs=outputs)
-            _raise_for_status(status, "solver='hip' (prepared)")
+                return general(True)
+            _raise_for_status(status, "solver='hip' (prepared)", sparse=prep.sparse)
     return out
 
 

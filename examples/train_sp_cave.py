@@ -10,6 +10,7 @@ BASELINE configs[0] sizes (5x5 grid, 100 instances, batch 32); `--problem tsp` i
     python examples/train_sp_cave.py --packed --graph          # the whole step (predictor, loss, backward, Adam) as one HIP graph
     python examples/train_sp_cave.py --problem tsp --prefetch  # dense cones: the next batch's pack rides in this batch's loss call
     python examples/train_sp_cave.py --sparse [--packed]       # cones on the sparse wire format: no dense padding anywhere
+    python examples/train_sp_cave.py --problem tsp --sparse --prefetch [--warm-start]  # the fused step packs the next SPARSE batch
 """
 
 import argparse
@@ -41,15 +42,15 @@ def main(argv=None):
                          "'ipm' (truncated interior-point iterate, as the reference's Clarabel max_iter=3: src/cave.py:213-214)")
     ap.add_argument("--max-iter", type=int, default=3, help="interior-point steps of --inner ipm")
     ap.add_argument("--warm-start", action="store_true",
-                    help="start each projection from the multipliers of the previous epoch (packed store, or dense cones "
-                         "through solver_kwargs={'warm_start': True})")
+                    help="start each projection from the multipliers of the previous epoch (packed store, or dense / --sparse "
+                         "cones through solver_kwargs={'warm_start': True})")
     ap.add_argument("--graph", action="store_true",
                     help="(with --packed, not hybrid) capture predictor + loss + backward + Adam of a full batch in ONE HIP "
                          "graph and replay it per step (the C-ABI launch path allocates nothing and never syncs when the "
                          "status check is off); a ragged last batch runs eagerly")
     ap.add_argument("--prefetch", action="store_true",
-                    help="(dense cones) wrap the DataLoader in cave_amd.dataset.prefetch: the loop body stays as it is and the "
-                         "pack stage of batch i+1 rides in the launch of batch i's loss")
+                    help="(dense or --sparse cones, not --packed) wrap the DataLoader in cave_amd.dataset.prefetch: the loop body "
+                         "stays as it is and the pack stage of batch i+1 rides in the launch of batch i's loss")
     ap.add_argument("--sparse", action="store_true",
                     help="the dataset hands out cones on the sparse wire format (cave_amd.sparse.SparseCones) and the loader "
                          "collates them with collate_sparse; with --packed the store is built by ConeStore.from_sparse")
@@ -57,8 +58,6 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.graph and (not args.packed or args.variant == "hybrid"):
         ap.error("--graph needs --packed and a variant without a per-call branch draw")
-    if args.sparse and not args.packed and (args.prefetch or args.warm_start):
-        ap.error("--sparse batches take neither --prefetch nor the dense warm start (they run cold)")
 
     from cave_amd.cave import EPO, exactConeAlignedCosine, innerConeAlignedCosine
     from cave_amd.dataset import ConeStore, PackedBatch, collate_sparse, prefetch
@@ -87,7 +86,7 @@ def main(argv=None):
     elif args.lazy_check:
         kw["check"] = "lazy"
     if args.warm_start and not args.packed:
-        kw["warm_start"] = True   # dense cones: the loss module's multiplier cache, keyed by cone content
+        kw["warm_start"] = True   # dense or sparse batches: the loss module's multiplier cache, keyed by cone content
     if args.variant == "exact":
         cave = exactConeAlignedCosine(_Model(), solver="hip", solver_kwargs=kw or None)
     elif args.variant == "inner":

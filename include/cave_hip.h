@@ -374,6 +374,29 @@ int32_t cave_hip_pack_large_sparse(const cave_sparse_cones* cones, int64_t nnz_c
                                    int32_t n_slots, int32_t* n_rows, int32_t* n_nnz, const cave_cone_store* store,
                                    int64_t slot0, int32_t* status, void* stream);
 
+/* The fused step with the NEXT batch on the sparse wire format (additive to v10): cave_hip_cone_step_warm with
+ * `next_ctrs, B_next, m_max, d` replaced by the batch -- 24 parameters.  The solve half is the same code reading the
+ * same lite store (it does not matter which route packed `solve`, so a chain may alternate dense and sparse batches);
+ * the pack half copies the coordinate list of each instance of `next_cones` instead of scanning a dense block, with
+ * the limits of the dense pack half (cave_hip_step_lds_bytes of next_cones->m_max, next_cones->d; the same non-zero
+ * capacity, the same arena): `next` and `pack_status` get the bits the dense route writes for the densified batch.
+ *   warm == NULL                                     the cold kernel
+ *   next_cones == NULL or next_cones->B == 0         solve only: exactly cave_hip_cone_step(_warm) without a pack half
+ *                                                    (the same kernel; d is solve->d)
+ *   B == 0                                           pack only
+ * Per instance of the pack half: an entry that breaks the contract above gives pack_status CAVE_ST_BAD_INPUT and
+ * slot state -1; more entries than the pack half keeps, or a cone the one-wave solver does not take, CAVE_ST_TOO_LARGE
+ * and slot state -1; an instance without entries is the empty cone (state 1).
+ * CAVE_E_INVALID before any launch: null or misaligned ent_off / key / val with next_cones->B > 0; next_cones->d
+ * different from a store's d; `next` the same store as `solve`; cu_tickets NULL; a shape the fused step does not take
+ * (cave_hip_step_lds_bytes < 0, or m_max = 0); a bad cache (as for cave_hip_cone_step_warm). */
+int32_t cave_hip_cone_step_sparse(const cave_lite_store* solve, const int64_t* ids, const float* pred, int64_t B, int32_t mode,
+                                  float sign, float inner_ratio, int32_t max_iter, int32_t flags, float* proj, float* rnorm,
+                                  float* target, float* loss, float* grad, int32_t* status, int32_t* iters,
+                                  const cave_sparse_cones* next_cones, const cave_lite_store* next, int32_t* pack_status,
+                                  const cave_warm_cache* warm, const int64_t* keys, uint8_t* warm_hit, uint32_t* cu_tickets,
+                                  void* stream);
+
 /* Device-resident stores: cones are static per instance (src/dataset.py:72), so a packed store whose cones qualify
  * builds the lite slots of ALL its instances once (slot i of `dst` from slot i of `src`, dst->n >= src->n) and then
  * serves batches of ids through the solve half of cave_hip_cone_step (no pack half).  status [src->n] or NULL:
