@@ -37,8 +37,10 @@
 // streamed once-read data (the dense cones): non-temporal loads leave the caches to the data that is re-read
 #if defined(__HIPCC__) && !defined(CAVE_SIMT_EMUL) && !defined(CAVE_NO_NT_LOADS)
 #define CAVE_NT_LOAD_F4(p) ::cave::nt_load_f4(p)
+#define CAVE_NT_LOAD_F32(p) __builtin_nontemporal_load(p)
 #else
 #define CAVE_NT_LOAD_F4(p) (*(p))
+#define CAVE_NT_LOAD_F32(p) (*(p))
 #endif
 #if defined(CAVE_SIMT_EMUL)
 #define CAVE_WAVE_ORDER() ::simt::wave_sync()
@@ -351,6 +353,11 @@ CAVE_HD uint32_t f2u(float f) {
   union { float f; uint32_t u; } x;
   x.f = f;
   return x.u;
+}
+CAVE_HD float u2f(uint32_t u) {
+  union { float f; uint32_t u; } x;
+  x.u = u;
+  return x.f;
 }
 
 }  // namespace cave

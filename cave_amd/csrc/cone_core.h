@@ -56,6 +56,7 @@ namespace cave {
 struct ConeBuild {
   int d, m;
   uint32_t nnz_all;  // non-zeros of the whole instance (row-major order)
+  uint32_t nnz_kept; // build_cone<C, true> only: entries in erc / eall (nnz_all minus the rows the scan classified itself)
   // ---- build-phase temporaries (top of the arena; dropped by Arena::release_top)
   uint32_t* erc;     // [cap] (row << 16) | col of every non-zero
   float* eall;       // [cap] its value
@@ -101,25 +102,35 @@ CAVE_HD uint8_t classify_row(float s1, float s2, bool allpm1, uint32_t len) {
 // Classify rows, detect +a/-a pairs, build compact CSR/CSC of the reduced rows.
 // Pre: cb.erc/eall hold the scan output in row-major order, cb.rptr the per-row counts
 // (m+1 entries, last = 0), cb.nnz_all set.  Returns ST_OK or ST_TOO_LARGE.
-template <class C>
+// PRESCAN (the row scan of the step kernel's dense pack half, BlockCtx::scan_rows): the producer has reserved and zeroed
+// ucnt, rs2 and rowtag itself (same order: the arena is the same), classified the rows with ONE non-zero -- tag, rs2 and
+// ucnt written, nothing stored, rptr[r] = 0 -- and tagged the short all-+-1 rows among the stored ones.  erc / eall hold
+// the cb.nnz_kept entries of the rows with two or more non-zeros; cb.nnz_all still counts every non-zero (it sizes
+// the long-row list as it always did).  A stored row with rowtag 0 is untagged and is classified here as before.
+template <class C, bool PRESCAN = false>
 CAVE_HD int32_t build_cone(C& c, Arena& ar, ConeBuild& cb) {
   const int d = cb.d, m = cb.m;
   const int NT = C::NT;
   CAVE_T0();
   // 1. row counts -> row pointers
   c.exclusive_scan_u32(cb.rptr, m + 1);
-  cb.ucnt = ar.get_top<uint32_t>(d);
-  cb.rs2 = ar.get_top<float>(m > 0 ? m : 1);
-  cb.rowtag = ar.get_top<uint8_t>(m > 0 ? m : 1);
+  if constexpr (!PRESCAN) {
+    cb.ucnt = ar.get_top<uint32_t>(d);
+    cb.rs2 = ar.get_top<float>(m > 0 ? m : 1);
+    cb.rowtag = ar.get_top<uint8_t>(m > 0 ? m : 1);
+  }
   const uint32_t nlong_cap = cb.nnz_all / kLongRow + 1u;
   uint32_t* longrows = ar.get_top<uint32_t>(nlong_cap);
   cb.usign = ar.get<uint8_t>(d);
   if (ar.ovf) return ST_TOO_LARGE;
-  for (int k = c.tid(); k < d; k += NT) cb.ucnt[k] = 0;
-  c.sync();
+  if constexpr (!PRESCAN) {
+    for (int k = c.tid(); k < d; k += NT) cb.ucnt[k] = 0;
+    c.sync();
+  }
   // 2. per-row statistics and tags (one thread per row; long rows are left pending)
   for (int r = c.tid(); r < m; r += NT) {
     const uint32_t lo = cb.rptr[r], hi = cb.rptr[r + 1];
+    if constexpr (PRESCAN) if (hi == lo || cb.rowtag[r] != 0) continue;  // nothing stored (empty, unit) or tagged by the scan
     if (hi - lo > kLongRow) { cb.rowtag[r] = ROW_PENDING; continue; }
     float s1 = 0.f, s2 = 0.f;
     bool allpm1 = true;
@@ -293,7 +304,8 @@ CAVE_HD int32_t build_cone(C& c, Arena& ar, ConeBuild& cb) {
   for (int k = c.tid(); k < d; k += NT) fill[k] = 0;
   c.sync();
   const bool pm1 = cb.pm1;
-  for (uint32_t e = c.tid(); e < cb.nnz_all; e += NT) {  // one thread per non-zero of the instance
+  const uint32_t nent = PRESCAN ? cb.nnz_kept : cb.nnz_all;
+  for (uint32_t e = c.tid(); e < nent; e += NT) {  // one thread per (stored) non-zero of the instance
     const uint32_t rc = cb.erc[e], r = rc >> 16, col = rc & 0xffffu;
     const uint32_t var = rowvar[r];
     if (var == 0xffffu) continue;
@@ -306,7 +318,7 @@ CAVE_HD int32_t build_cone(C& c, Arena& ar, ConeBuild& cb) {
   c.sync();
   c.exclusive_scan_u32(cb.cptr, d + 1);
   c.sync();
-  for (uint32_t e = c.tid(); e < cb.nnz_all; e += NT) {
+  for (uint32_t e = c.tid(); e < nent; e += NT) {
     const uint32_t rc = cb.erc[e], r = rc >> 16, col = rc & 0xffffu;
     const uint32_t var = rowvar[r];
     if (var == 0xffffu) continue;

@@ -96,8 +96,11 @@ CAVE_HD void fill_failure(C& c, int d, int64_t b, const OutPtrs& o) {
 
 // scan the dense block + build the reduced cone; returns status
 // (LARGE: the arena is global memory -> predicated scan stores, no dump slots)
-// DEEP (multi-wave contexts with the 256-register budget: the step kernel's pack half): BlockCtx::scan_dense_sparse,
-// predicated stores -- no dump slots behind the scan output
+// DEEP (multi-wave contexts with the 256-register budget: the step kernel's pack half, d <= 256): BlockCtx::scan_rows,
+// predicated stores -- no dump slots behind the scan output.  The scan is row-structured: it classifies the rows with
+// one non-zero (the +-e_k rows: most rows of a TSP cone) while they are in registers and stores only the entries of the
+// rows with two or more, already as (row << 16) | col with their per-row counts; build_cone<C, true> takes it from there.
+// The arena is the one of the flat form: ucnt, rs2 and rowtag are reserved (and zeroed) here, in build_cone's order.
 template <class C, bool LARGE = false, bool DEEP = false>
 CAVE_HD int32_t scan_and_build(C& c, Arena& ar, ConeBuild& cb, const float* A, int m, int d, uint32_t cap) {
   cb.d = d;
@@ -110,12 +113,31 @@ CAVE_HD int32_t scan_and_build(C& c, Arena& ar, ConeBuild& cb, const float* A, i
   cb.eall = ar.get_top<float>(cap + dump_slots);
   cb.rptr = ar.get_top<uint32_t>((uint32_t)m + 1u);
   if (ar.ovf) return ST_TOO_LARGE;
+  if constexpr (DEEP) {
+    if (d > 256) return ST_TOO_LARGE;  // (one wave pass sees a whole row; step_limits refuses a larger d)
+    cb.ucnt = ar.get_top<uint32_t>(d);
+    cb.rs2 = ar.get_top<float>(m > 0 ? m : 1);
+    cb.rowtag = ar.get_top<uint8_t>(m > 0 ? m : 1);
+    if (ar.ovf) return ST_TOO_LARGE;
+    for (int r = c.tid(); r <= m; r += C::NT) cb.rptr[r] = 0u;
+    for (int k = c.tid(); k < d; k += C::NT) cb.ucnt[k] = 0u;
+    for (int r = c.tid(); r < m; r += C::NT) { cb.rs2[r] = 0.f; cb.rowtag[r] = 0; }
+    c.sync();
+    CAVE_T0();
+    uint32_t stored = 0;
+    const uint32_t nnz = c.template scan_rows<8>(A, (uint32_t)m, (uint32_t)d, cb.erc, cb.eall, cb.rptr, cb.ucnt, cb.rs2,
+                                                 cb.rowtag, cap, stored);
+    c.sync();
+    CAVE_ACC(10);
+    if (nnz > cap) return ST_TOO_LARGE;  // every non-zero counts, the unit rows' too: the verdicts of the flat form
+    cb.nnz_all = nnz;
+    cb.nnz_kept = stored;
+    return build_cone<C, true>(c, ar, cb);
+  } else {
   for (int r = c.tid(); r <= m; r += C::NT) cb.rptr[r] = 0u;
   c.sync();
   CAVE_T0();
-  uint32_t nnz;  // (erc = flat index for now)
-  if constexpr (DEEP) nnz = c.template scan_dense_sparse<8>(A, (uint32_t)m * (uint32_t)d, cb.erc, cb.eall, cap);
-  else nnz = c.template scan_dense<LARGE>(A, (uint32_t)m * (uint32_t)d, cb.erc, cb.eall, cap);
+  uint32_t nnz = c.template scan_dense<LARGE>(A, (uint32_t)m * (uint32_t)d, cb.erc, cb.eall, cap);  // (erc = flat index for now)
   c.sync();
   CAVE_ACC(10);
   if (nnz > cap) return ST_TOO_LARGE;
@@ -133,6 +155,7 @@ CAVE_HD int32_t scan_and_build(C& c, Arena& ar, ConeBuild& cb, const float* A, i
   c.sync();
   cb.nnz_all = nnz;
   return build_cone(c, ar, cb);
+  }
 }
 
 // 16-byte groups of the sparse wire format (plain vector types: the serial and SIMT test builds have no float4)

@@ -12,8 +12,16 @@
 #pragma once
 #include "wave_prims.h"
 #include "ctx_wave.h"
+#include "cone_core.h"  // classify_row, kLongRow: the row scan of the step kernel's pack half tags rows
 
 namespace cave {
+
+// ballot of a wave64 as ONE compare that writes the mask (HIP's __ballot goes through a 0 / 1 select and a second compare)
+#if defined(__HIPCC__) && !defined(CAVE_SIMT_EMUL)
+__device__ __forceinline__ uint64_t ballot64(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+#else
+__device__ __forceinline__ uint64_t ballot64(bool p) { return __ballot(p); }
+#endif
 
 // SoloCtx — the Newton iteration of a SMALL +-1 cone on ONE wave (wave 0 of a multi-wave workgroup, the other
 // waves parked at the workgroup barrier that follows; or the only wave of a one-wave workgroup), over the
@@ -310,108 +318,172 @@ struct BlockCtx {
     if (done < n) scan_single(A, done, n, cursor, eflat, eval, cap);
     return cursor;
   }
-  // The scan of the step kernel's pack half (256-register budget), same contract and output order as scan_dense but
-  // PREDICATED stores (no dump slots: eflat / eval hold `cap` entries), for SPARSE cones -- what this domain has: a
-  // TSP-20 instance holds ~1 100 non-zeros in 44 080 elements, one or two per KiB.  scan_dense runs ~100 instructions
-  // per KiB chunk whatever it holds; here a chunk costs ~8 when it is empty (one OR-test + ballot), ~45 when no lane
-  // holds more than one non-zero (ONE ballot + mbcnt gives the slots; the lanes with a non-zero store it under their
-  // exec mask), the full four-ballot form only when some lane's float4 holds two or more (runs of consecutive edges
-  // in TSP degree / cut rows).  U = 8 KiB per wave per batch: deeper batches (16: 32 KiB in flight per wave) shorten a
-  // LONE workgroup's scan (tools/micro/stream_wg.hip: ~5 k cycles of memory latency per round trip) but not the
-  // step kernel's, which runs two to four pack workgroups per compute unit beside the solve waves and is bound by
-  // issue and instruction fetch (SQ_WAIT_INST_ANY 20 % of its wave cycles): U = 4 / 8 / 16 -> pack-only launch 66.4 /
-  // 66.5 / 71.9 us, fused step 133.5 / 133.2 / 135.7 us.
-  // Tried and dropped (round 4, same timing within 5 %): dword loads with one element per lane and a wave's whole
-  // share resident in registers (one ballot per 64 floats, one barrier per round, buffer-load range checks).
+  // The scan of the step kernel's pack half (256-register budget) for SPARSE cones of at most 256 columns -- what this
+  // domain has: a TSP-20 instance holds ~1 100 non-zeros in 235 rows of 190, and 190 of those rows are +-e_k rows with
+  // one non-zero each.  ROW-structured: a wave takes whole rows (U consecutive rows per batch, two batches in flight, the
+  // rows of a round dealt wave-major), one dword per lane and ceil(d / 64) <= 4 coalesced non-temporal loads per row (a
+  // row starts wherever r * d puts it: nothing wider than 4 bytes is aligned), so the ballot of a load IS the column
+  // mask of 64 columns and everything a row needs is decided from wave-uniform masks while it is in registers:
+  //   no non-zero   nothing is written (rptr[r] stays 0)
+  //   exactly one   a unit row: it only ever contributes its tag, ucnt[col] and the valid-row counts, so it is
+  //                 classified here (classify_row on |v|, v^2, |v| == 1, length 1: the sums build_cone forms for a
+  //                 one-entry row) and NOT stored: rowtag[r], rs2[r], ucnt[col] (+1 / +0x10000 by v > 0 unless the row
+  //                 is dropped -- a NaN row is), rptr[r] stays 0
+  //   two or more   the entries go to erc / eall in row-major order, already as (r << 16) | col, rptr[r] = their number;
+  //                 a row of at most kLongRow entries that are all +-1 has s1 = s2 = that number exactly and is tagged
+  //                 here too; any other row keeps rowtag[r] = 0 (untagged) for build_cone's serial / long-row passes,
+  //                 whose float sums keep their order
+  // The single value / the count of a row is handed to lane u of the wave (u: the row's place in the batch) and the LDS
+  // writes of a batch's rows are made by those U lanes at once.  NaN counts as a non-zero, +-0 does not (the bit test).
+  // One barrier per round (LDS only: the prefetched batch stays in flight) turns the per-wave counts into slot bases.
+  // Pre: rptr, ucnt, rs2 and rowtag are zeroed.  Returns ALL non-zeros (unit rows included: what `cap` is tested against);
+  // `stored` = the entries written to erc / eall (slots >= cap are not written).
+  // Replaces scan_dense_sparse (flat 1 KiB chunks, every non-zero stored by flat index; the flat index -> row/col pass,
+  // the one-thread-per-row classification and the unit entries in the CSR / CSC loops came after it).
+  // KD = ceil(d / 64) is a template parameter: the loads of a batch are then straight-line code (a load inside a branch,
+  // even a uniform one, makes the compiler wait for EVERY load in flight before the first use -- the prefetched batch too)
   template <int U>
-  __device__ __forceinline__ uint32_t scan_dense_sparse(const float* __restrict__ A, uint32_t n, uint32_t* eflat, float* eval,
-                                                        uint32_t cap) {
-    static_assert(U <= 16, "component masks of a batch are packed into 64 bits");
-    uint32_t cursor = 0;
-    uint32_t head = (uint32_t)(((16u - (uint32_t)((uintptr_t)A & 15u)) & 15u) >> 2);
-    if (head > n) head = n;
-    if (head) scan_single(A, 0u, head, cursor, eflat, eval, cap);
-    const float4* __restrict__ A4 = reinterpret_cast<const float4*>(A + head);
-    const uint32_t n4 = (n - head) >> 2;
-    const uint32_t round = 64u * U * NW;
-    const uint32_t woff = (uint32_t)wave * 64u * U + (uint32_t)lane;
-    float4 bufA[U], bufB[U];
-    auto load_batch = [&](float4* buf, uint32_t r0) {
+  __device__ __forceinline__ uint32_t scan_rows(const float* __restrict__ A, uint32_t m, uint32_t d, uint32_t* erc, float* eall,
+                                                uint32_t* rptr, uint32_t* ucnt, float* rs2, uint8_t* rowtag, uint32_t cap,
+                                                uint32_t& stored) {
+    if (d <= 64u) return scan_rows_kd<U, 1>(A, m, d, erc, eall, rptr, ucnt, rs2, rowtag, cap, stored);
+    if (d <= 128u) return scan_rows_kd<U, 2>(A, m, d, erc, eall, rptr, ucnt, rs2, rowtag, cap, stored);
+    if (d <= 192u) return scan_rows_kd<U, 3>(A, m, d, erc, eall, rptr, ucnt, rs2, rowtag, cap, stored);
+    return scan_rows_kd<U, 4>(A, m, d, erc, eall, rptr, ucnt, rs2, rowtag, cap, stored);
+  }
+  template <int U, int KD>
+  __device__ __forceinline__ uint32_t scan_rows_kd(const float* __restrict__ A, uint32_t m, uint32_t d, uint32_t* erc, float* eall,
+                                                   uint32_t* rptr, uint32_t* ucnt, float* rs2, uint8_t* rowtag, uint32_t cap,
+                                                   uint32_t& stored) {
+    static_assert(KD <= 4 && U <= 64 && (uint32_t)U * 64u * KD * NW < 0x8000u, "per-round counts travel as two 16-bit halves of one word");
+    // (the wave index as a scalar: row numbers, row addresses and the tests on them are then scalar too)
+    const uint32_t round = (uint32_t)(U * NW), wrow = (uint32_t)__builtin_amdgcn_readfirstlane(wave) * (uint32_t)U;
+    // this lane's column of load j; only the last load of a row can reach past it (64 (KD - 1) < d <= 64 KD): clamped
+    // into the row there, and masked out of the ballots
+    uint32_t coff[KD];
+#pragma unroll
+    for (int j = 0; j < KD; ++j) coff[j] = (uint32_t)lane + 64u * (uint32_t)j;
+    const bool cin_last = coff[KD - 1] < d;
+    if (!cin_last) coff[KD - 1] = d - 1u;
+    auto is_nz = [&](float v, int j) {  // (+-0 have no bits below the sign; NaN counts, as `x != 0.0f` does)
+      const bool b = (f2u(v) & 0x7fffffffu) != 0u;
+      return j == KD - 1 ? (b && cin_last) : b;
+    };
+    float bufA[U][KD], bufB[U][KD];
+    auto load_batch = [&](auto& buf, uint32_t r0) {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        uint32_t i = r0 + woff + (uint32_t)u * 64u;
-        buf[u] = CAVE_NT_LOAD_F4(&A4[i < n4 ? i : n4 - 1u]);  // unconditional dwordx4 from a clamped index; read once: nt
+        const uint32_t r = r0 + wrow + (uint32_t)u;
+        const float* __restrict__ row = A + (size_t)(r < m ? r : m - 1u) * d;  // unconditional loads from a clamped row; read once: nt
+#pragma unroll
+        for (int j = 0; j < KD; ++j) buf[u][j] = CAVE_NT_LOAD_F32(row + coff[j]);
       }
     };
-    auto scan_batch = [&](const float4* buf, uint32_t r0) {
-      uint32_t rel[U], wsum = 0;
-      uint64_t nzm = 0;            // 4 bits per chunk: this lane's component mask
-      uint32_t anym = 0, multim = 0;  // wave-uniform, one bit per chunk: not empty / some lane holds two or more
+    uint32_t cursor = 0, nall = 0;
+    auto scan_batch = [&](const auto& buf, uint32_t r0) {
+      uint32_t cnt[U], rel[U];  // wave-uniform
+      uint32_t wsum = 0, wall = 0;
+      uint32_t info = 0;  // lane u: row u's count (low 15 bits) | 0x8000 every entry +-1 | column of a unit row << 16
+      float uval = 0.0f;  // lane u: value of unit row u
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        const uint32_t i = r0 + woff + (uint32_t)u * 64u;
-        const float4 v = buf[u];
-        // any non-zero in this lane's float4?  (+-0 have no bits below the sign; NaN counts, as `x != 0.0f` does)
-        const uint32_t bits = (f2u(v.x) | f2u(v.y) | f2u(v.z) | f2u(v.w)) & 0x7fffffffu;
-        const bool mine = bits != 0u && i < n4;
-        const uint64_t any = __ballot(mine);
+        cnt[u] = 0u;
         rel[u] = wsum;
-        if (any == 0ull) continue;  // wave-uniform: the chunk is empty
-        anym |= 1u << u;
-        const uint32_t n0 = mine && v.x != 0.0f, n1 = mine && v.y != 0.0f, n2 = mine && v.z != 0.0f, n3 = mine && v.w != 0.0f;
-        const uint32_t m4 = n0 | (n1 << 1) | (n2 << 2) | (n3 << 3);
-        nzm |= (uint64_t)m4 << (4 * u);
-        const uint64_t multi = __ballot((m4 & (m4 - 1u)) != 0u);
-        if (multi == 0ull) {  // wave-uniform: one non-zero per lane at most
-          rel[u] += mbcnt64(any);
-          wsum += (uint32_t)__popcll(any);
-        } else {
-          multim |= 1u << u;
-          const uint64_t m0 = __ballot(n0 != 0u), m1 = __ballot(n1 != 0u), m2 = __ballot(n2 != 0u), m3 = __ballot(n3 != 0u);
-          rel[u] += mbcnt64(m0) + mbcnt64(m1) + mbcnt64(m2) + mbcnt64(m3);
-          wsum += (uint32_t)(__popcll(m0) + __popcll(m1) + __popcll(m2) + __popcll(m3));
+        if (r0 + wrow + (uint32_t)u >= m) continue;  // wave-uniform
+        bool nz[KD];
+        uint64_t mk[KD];
+        uint32_t n = 0;
+#pragma unroll
+        for (int j = 0; j < KD; ++j) {
+          nz[j] = is_nz(buf[u][j], j);
+          mk[j] = ballot64(nz[j]);
+          n += (uint32_t)__popcll(mk[j]);
+        }
+        cnt[u] = n;
+        wall += n;
+        if (n == 1u) {
+          // (one entry in the whole row: its bits are the OR over the loads.  Not a chain of selects between the
+          //  registers of the batch: the compiler turns that into an indexed load and moves the batch to scratch memory)
+          uint32_t mine = 0u, jj = 0u;
+          uint64_t any = 0ull;
+#pragma unroll
+          for (int j = 0; j < KD; ++j) {
+            mine |= nz[j] ? f2u(buf[u][j]) : 0u;
+            jj |= mk[j] ? (uint32_t)j : 0u;
+            any |= mk[j];
+          }
+          const int src = __ffsll((unsigned long long)any) - 1;
+          const uint32_t sv = (uint32_t)__builtin_amdgcn_readlane((int)mine, src);
+          if (lane == u) { info = 1u | ((64u * jj + (uint32_t)src) << 16); uval = u2f(sv); }
+        } else if (n >= 2u) {
+          uint64_t other = 0;  // entries that are not +-1 (NaN among them)
+#pragma unroll
+          for (int j = 0; j < KD; ++j) other |= ballot64(nz[j] && fabsf(buf[u][j]) != 1.0f);
+          wsum += n;
+          if (lane == u) info = n | (other == 0ull ? 0x8000u : 0u);
         }
       }
       uint32_t pre, tot;
-      wave_prefix(wsum, pre, tot);
-      if (tot != 0u) {  // workgroup-uniform
-        const uint32_t base = cursor + pre;
+      wave_prefix(wsum | (wall << 16), pre, tot);
+      if (wsum != 0u) {  // wave-uniform
+        const uint32_t base = cursor + (pre & 0xffffu);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-          if (!((anym >> u) & 1u)) continue;  // wave-uniform
-          const uint32_t i = r0 + woff + (uint32_t)u * 64u;
-          const uint32_t m4 = (uint32_t)(nzm >> (4 * u)) & 15u;
-          const uint32_t f = head + 4u * i, p0 = base + rel[u];
-          const float4 v = buf[u];
-          if (!((multim >> u) & 1u)) {
-            if (m4 != 0u && p0 < cap) {  // the lanes holding the chunk's non-zeros (one each)
-              const uint32_t comp = (uint32_t)__builtin_ctz(m4);
-              eflat[p0] = f + comp;
-              eval[p0] = (m4 & 1u) ? v.x : (m4 & 2u) ? v.y : (m4 & 4u) ? v.z : v.w;
+          if (cnt[u] < 2u) continue;  // wave-uniform
+          const uint32_t r = r0 + wrow + (uint32_t)u;
+          uint32_t pos = base + rel[u];
+#pragma unroll
+          for (int j = 0; j < KD; ++j) {
+            const float v = buf[u][j];
+            // (the mask is formed again, one compare, and not kept from the classification loop: U * KD 64-bit masks
+            //  held across the barrier are 48 - 64 scalar registers, and this kernel already spills ~450 of them; only
+            //  the rows with two or more entries -- 45 of 235 at TSP-20 -- come here)
+            const bool mine = is_nz(v, j);
+            const uint64_t mkj = ballot64(mine);
+            if (mkj == 0ull) continue;  // wave-uniform
+            const uint32_t p = pos + mbcnt64(mkj);
+            if (mine && p < cap) {
+              erc[p] = (r << 16) | ((uint32_t)lane + 64u * (uint32_t)j);
+              eall[p] = v;
             }
-          } else {
-            const uint32_t p1 = p0 + (m4 & 1u), p2 = p1 + ((m4 >> 1) & 1u), p3 = p2 + ((m4 >> 2) & 1u);
-            if ((m4 & 1u) && p0 < cap) { eflat[p0] = f; eval[p0] = v.x; }
-            if ((m4 & 2u) && p1 < cap) { eflat[p1] = f + 1u; eval[p1] = v.y; }
-            if ((m4 & 4u) && p2 < cap) { eflat[p2] = f + 2u; eval[p2] = v.z; }
-            if ((m4 & 8u) && p3 < cap) { eflat[p3] = f + 3u; eval[p3] = v.w; }
+            pos += (uint32_t)__popcll(mkj);
           }
         }
       }
-      cursor += tot;
-    };
-    if (n4 > 0) load_batch(bufA, 0);
-    for (uint32_t r0 = 0; r0 < n4; r0 += 2u * round) {
-      if (r0 + round < n4) load_batch(bufB, r0 + round);
-      scan_batch(bufA, r0);
-      if (r0 + round < n4) {
-        if (r0 + 2u * round < n4) load_batch(bufA, r0 + 2u * round);
-        scan_batch(bufB, r0 + round);
+      cursor += tot & 0xffffu;
+      nall += tot >> 16;
+      // the rows of this batch: lane u writes what row u leaves in LDS
+      const uint32_t n = info & 0x7fffu;
+      if (n != 0u) {
+        const uint32_t r = r0 + wrow + (uint32_t)lane;
+        if (n == 1u) {
+          const float s2 = uval * uval;
+          const uint8_t tag = classify_row(fabsf(uval), s2, fabsf(uval) == 1.0f, 1u);
+          rowtag[r] = tag;
+          rs2[r] = s2;
+          if ((tag & 0x0F) == ROW_UNIT) atomic_add_u32(&ucnt[info >> 16], uval > 0.f ? 1u : 0x10000u);
+        } else {
+          rptr[r] = n;
+          if ((info & 0x8000u) && n <= kLongRow) {
+            rowtag[r] = classify_row((float)n, (float)n, true, n);
+            rs2[r] = (float)n;
+          }
+        }
       }
+    };
+    // The next batch is requested UNCONDITIONALLY, also past the last row (clamped: the last row again): with the request
+    // inside a branch the compiler's wait-count bookkeeping assumes at the join that it was not made, and every use of
+    // the batch being scanned then waits for the prefetched one as well -- no overlap at all.  A batch past the last row
+    // scans nothing (its rows are skipped) but meets the other waves at the barrier.
+    if (m > 0u) load_batch(bufA, 0u);
+    for (uint32_t r0 = 0; r0 < m; r0 += 2u * round) {
+      load_batch(bufB, r0 + round);
+      scan_batch(bufA, r0);
+      load_batch(bufA, r0 + 2u * round);
+      scan_batch(bufB, r0 + round);
     }
-    const uint32_t done = head + 4u * n4;
-    if (done < n) scan_single(A, done, n, cursor, eflat, eval, cap);
-    return cursor;
+    stored = cursor;
+    return nall;
   }
   // fewer than 64 stray elements [lo, hi): wave 0, one per lane
   __device__ __forceinline__ void scan_single(const float* __restrict__ A, uint32_t lo, uint32_t hi, uint32_t& cursor,

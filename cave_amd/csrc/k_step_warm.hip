@@ -2,7 +2,7 @@
 // as k_step.hip with the cache probe / write-back in its solve half, built in a translation unit of its own so that the
 // cold kernel's code object does not change.  The wave priorities are those of k_step.hip (see the measurements there).
 #ifndef CAVE_LITE_TAIL_PRIO_IT
-#define CAVE_LITE_TAIL_PRIO_IT 6
+#define CAVE_LITE_TAIL_PRIO_IT 5
 #endif
 #ifndef CAVE_STEP_PACK_PRIO
 #define CAVE_STEP_PACK_PRIO 2
