@@ -23,7 +23,7 @@ _HEADERS = [os.path.join(_CSRC, n) for n in ("kernels.h", "cone_common.h", "cone
 # translation units: the C ABI (host code) + one file per kernel shape (cave_amd/csrc/kernels.h)
 _UNITS = ["cave_hip"] + [f"k_{op}_w{w}" for op in ("dense", "pack", "packed") for w in (1, 2, 4, 8)] + \
     ["k_large_dense", "k_large_pack", "k_large_packed_w1", "k_large_packed_w2", "k_large_packed_w4", "k_step",
-     "k_step_warm", "k_step_sparse", "k_step_sparse_warm", "k_pack_sparse_w2", "k_pack_sparse_w4", "k_pack_sparse_w8", "k_large_pack_sparse"]
+     "k_step_warm", "k_step_sparse", "k_step_sparse_warm", "k_step_ipm", "k_step_sparse_ipm", "k_pack_sparse_w2", "k_pack_sparse_w4", "k_pack_sparse_w8", "k_large_pack_sparse"]
 _SOURCES = [os.path.join(_CSRC, u + ".hip") for u in _UNITS] + _HEADERS
 _OBJ_DIR = os.path.join(_CSRC, "build")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
@@ -41,7 +41,7 @@ ABI_SYMBOLS = (
     "cave_hip_pack_large", "cave_hip_cone_packed_large", "cave_hip_packed_large_lds_bytes", "cave_hip_packed_large_rb_bytes",
     "cave_hip_step_lds_bytes", "cave_hip_cone_step", "cave_hip_lite_from_packed", "cave_hip_cone_step_warm",
     "cave_hip_pack_count_sparse", "cave_hip_pack_fill_sparse", "cave_hip_pack_large_sparse",
-    "cave_hip_cone_step_sparse",
+    "cave_hip_cone_step_sparse", "cave_hip_cone_step_ipm", "cave_hip_cone_step_sparse_ipm",
 )
 
 
@@ -183,6 +183,12 @@ def load_library() -> C.CDLL:
                                               vp, C.POINTER(SparseConesC), C.POINTER(LiteStore), vp, C.POINTER(WarmCacheC),
                                               vp, vp, vp, vp]
     lib.cave_hip_cone_step_sparse.restype = i32
+    lib.cave_hip_cone_step_ipm.argtypes = [C.POINTER(LiteStore), vp, vp, i64, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp,
+                                           vp, i64, i64, i64, C.POINTER(LiteStore), vp, vp, vp]
+    lib.cave_hip_cone_step_ipm.restype = i32
+    lib.cave_hip_cone_step_sparse_ipm.argtypes = [C.POINTER(LiteStore), vp, vp, i64, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp,
+                                                  C.POINTER(SparseConesC), C.POINTER(LiteStore), vp, vp, vp]
+    lib.cave_hip_cone_step_sparse_ipm.restype = i32
     _lib = lib
     return lib
 

@@ -390,7 +390,8 @@ static int32_t cone_step_impl(const cave_lite_store* solve, const int64_t* ids, 
                               float* target, float* loss, float* grad, int32_t* status, int32_t* iters, const float* next_ctrs,
                               int64_t B_next, int64_t m_max, int64_t d, const cave_lite_store* next, int32_t* pack_status,
                               const cave_warm_cache* warm, const int64_t* keys, uint8_t* warm_hit, uint32_t* cu_tickets,
-                              void* stream) {
+                              void* stream, bool ipm = false) {
+  // ipm: the interior-point variant (cave_hip_cone_step_ipm: mode is CAVE_MODE_INNER_IPM, no cache, max_iter <= 0 = 3)
   if (warm) {
     const int64_t n = warm->n_entries;
     if (n <= 0 || n >= (int64_t)1 << 40 || (n & (n - 1)) != 0)
@@ -405,11 +406,11 @@ static int32_t cone_step_impl(const cave_lite_store* solve, const int64_t* ids, 
   StepParams P;
   memset(&P, 0, sizeof(P));
   if (B > 0) {
-    if (mode < CAVE_MODE_PROJECT || mode > CAVE_MODE_AVG) return fail(CAVE_E_INVALID, "cone_step: bad mode (PROJECT .. AVG)");
+    if (!ipm && (mode < CAVE_MODE_PROJECT || mode > CAVE_MODE_AVG)) return fail(CAVE_E_INVALID, "cone_step: bad mode (PROJECT .. AVG)");
     if (!pred && mode != CAVE_MODE_AVG) return fail(CAVE_E_INVALID, "cone_step: pred is null");
     if (!lite_store_ok(solve, ids ? 1 : B, d)) return fail(CAVE_E_INVALID, "cone_step: bad solve store (size, d, null or unaligned array)");
     P.S.store = *solve; P.S.ids = ids; P.S.pred = pred; P.S.B = B; P.S.mode = mode; P.S.sign = sign; P.S.inner_ratio = inner_ratio;
-    P.S.max_iter = max_iter > 0 ? max_iter : 100;
+    P.S.max_iter = max_iter > 0 ? max_iter : (ipm ? 3 : 100);
     P.S.flags = flags;
     P.S.o = OutPtrs{proj, rnorm, target, loss, grad, status, iters};
   }
@@ -440,6 +441,11 @@ static int32_t cone_step_impl(const cave_lite_store* solve, const int64_t* ids, 
   }
   hipError_t e = warm_hit && B > 0 ? hipMemsetAsync(warm_hit, 0, (size_t)B, (hipStream_t)stream) : hipSuccess;
   if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "cone_step: warm_hit", e);
+  if (ipm && B > 0) {  // (a pack-only launch: the cold kernel's pack half is the same code)
+    e = launch_step_ipm((unsigned)(B + B_next), (uint32_t)lds, (hipStream_t)stream, P);
+    if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch cone_step_kernel (ipm)", e);
+    return CAVE_OK;
+  }
   e = launch_step((unsigned)(B + B_next), (uint32_t)lds, (hipStream_t)stream, P);
   if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch cone_step_kernel", e);
   return CAVE_OK;
@@ -466,17 +472,17 @@ int32_t cave_hip_cone_step_warm(const cave_lite_store* solve, const int64_t* ids
 
 // the fused step with the NEXT batch on the sparse wire format (kernels.h cone_step_sparse_kernel): the solve half and
 // its arguments are those of cave_hip_cone_step_warm, the pack half reads `next_cones`
-int32_t cave_hip_cone_step_sparse(const cave_lite_store* solve, const int64_t* ids, const float* pred, int64_t B, int32_t mode,
-                                  float sign, float inner_ratio, int32_t max_iter, int32_t flags, float* proj, float* rnorm,
-                                  float* target, float* loss, float* grad, int32_t* status, int32_t* iters,
-                                  const cave_sparse_cones* next_cones, const cave_lite_store* next, int32_t* pack_status,
-                                  const cave_warm_cache* warm, const int64_t* keys, uint8_t* warm_hit, uint32_t* cu_tickets,
-                                  void* stream) {
+static int32_t cone_step_sparse_impl(const cave_lite_store* solve, const int64_t* ids, const float* pred, int64_t B, int32_t mode,
+                                     float sign, float inner_ratio, int32_t max_iter, int32_t flags, float* proj, float* rnorm,
+                                     float* target, float* loss, float* grad, int32_t* status, int32_t* iters,
+                                     const cave_sparse_cones* next_cones, const cave_lite_store* next, int32_t* pack_status,
+                                     const cave_warm_cache* warm, const int64_t* keys, uint8_t* warm_hit, uint32_t* cu_tickets,
+                                     void* stream, bool ipm) {
   if (!next_cones || next_cones->B == 0) {
     // solve only: the dense entry point's launch (the same kernel, the same bits); d is the store's
     if (B > 0 && !solve) return fail(CAVE_E_INVALID, "cone_step_sparse: solve store is null");
     return cone_step_impl(solve, ids, pred, B, mode, sign, inner_ratio, max_iter, flags, proj, rnorm, target, loss, grad, status,
-                          iters, nullptr, 0, 0, solve ? solve->d : 1, nullptr, nullptr, warm, keys, warm_hit, cu_tickets, stream);
+                          iters, nullptr, 0, 0, solve ? solve->d : 1, nullptr, nullptr, warm, keys, warm_hit, cu_tickets, stream, ipm);
   }
   if (warm) {
     const int64_t n = warm->n_entries;
@@ -500,12 +506,12 @@ int32_t cave_hip_cone_step_sparse(const cave_lite_store* solve, const int64_t* i
   StepSparseParams P;
   memset(&P, 0, sizeof(P));
   if (B > 0) {
-    if (mode < CAVE_MODE_PROJECT || mode > CAVE_MODE_AVG) return fail(CAVE_E_INVALID, "cone_step_sparse: bad mode (PROJECT .. AVG)");
+    if (!ipm && (mode < CAVE_MODE_PROJECT || mode > CAVE_MODE_AVG)) return fail(CAVE_E_INVALID, "cone_step_sparse: bad mode (PROJECT .. AVG)");
     if (!pred && mode != CAVE_MODE_AVG) return fail(CAVE_E_INVALID, "cone_step_sparse: pred is null");
     if (!lite_store_ok(solve, ids ? 1 : B, d)) return fail(CAVE_E_INVALID, "cone_step_sparse: bad solve store (size, d, null or unaligned array)");
     if (next->hdr == solve->hdr) return fail(CAVE_E_INVALID, "cone_step_sparse: solve and next must be different stores");
     P.S.store = *solve; P.S.ids = ids; P.S.pred = pred; P.S.B = B; P.S.mode = mode; P.S.sign = sign; P.S.inner_ratio = inner_ratio;
-    P.S.max_iter = max_iter > 0 ? max_iter : 100;
+    P.S.max_iter = max_iter > 0 ? max_iter : (ipm ? 3 : 100);
     P.S.flags = flags;
     P.S.o = OutPtrs{proj, rnorm, target, loss, grad, status, iters};
   }
@@ -527,9 +533,45 @@ int32_t cave_hip_cone_step_sparse(const cave_lite_store* solve, const int64_t* i
   }
   hipError_t e = warm_hit && B > 0 ? hipMemsetAsync(warm_hit, 0, (size_t)B, (hipStream_t)stream) : hipSuccess;
   if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "cone_step_sparse: warm_hit", e);
+  if (ipm && B > 0) {  // (a pack-only launch: the cold kernel's pack half is the same code)
+    e = launch_step_sparse_ipm((unsigned)(B + B_next), (uint32_t)lds, (hipStream_t)stream, P);
+    if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch cone_step_sparse_kernel (ipm)", e);
+    return CAVE_OK;
+  }
   e = launch_step_sparse((unsigned)(B + B_next), (uint32_t)lds, (hipStream_t)stream, P);
   if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch cone_step_sparse_kernel", e);
   return CAVE_OK;
+}
+
+int32_t cave_hip_cone_step_sparse(const cave_lite_store* solve, const int64_t* ids, const float* pred, int64_t B, int32_t mode,
+                                  float sign, float inner_ratio, int32_t max_iter, int32_t flags, float* proj, float* rnorm,
+                                  float* target, float* loss, float* grad, int32_t* status, int32_t* iters,
+                                  const cave_sparse_cones* next_cones, const cave_lite_store* next, int32_t* pack_status,
+                                  const cave_warm_cache* warm, const int64_t* keys, uint8_t* warm_hit, uint32_t* cu_tickets,
+                                  void* stream) {
+  return cone_step_sparse_impl(solve, ids, pred, B, mode, sign, inner_ratio, max_iter, flags, proj, rnorm, target, loss, grad,
+                               status, iters, next_cones, next, pack_status, warm, keys, warm_hit, cu_tickets, stream, false);
+}
+
+// ---- the interior-point variant of the fused step (CAVE_MODE_INNER_IPM): kernels of their own (k_step_ipm.hip,
+// k_step_sparse_ipm.hip), validated as their siblings; always cold
+int32_t cave_hip_cone_step_ipm(const cave_lite_store* solve, const int64_t* ids, const float* pred, int64_t B, float sign,
+                               int32_t max_iter, int32_t flags, float* proj, float* rnorm, float* target, float* loss,
+                               float* grad, int32_t* status, int32_t* iters, const float* next_ctrs, int64_t B_next,
+                               int64_t m_max, int64_t d, const cave_lite_store* next, int32_t* pack_status,
+                               uint32_t* cu_tickets, void* stream) {
+  return cone_step_impl(solve, ids, pred, B, CAVE_MODE_INNER_IPM, sign, 0.0f, max_iter, flags, proj, rnorm, target, loss, grad,
+                        status, iters, next_ctrs, B_next, m_max, d, next, pack_status, nullptr, nullptr, nullptr, cu_tickets,
+                        stream, true);
+}
+
+int32_t cave_hip_cone_step_sparse_ipm(const cave_lite_store* solve, const int64_t* ids, const float* pred, int64_t B, float sign,
+                                      int32_t max_iter, int32_t flags, float* proj, float* rnorm, float* target, float* loss,
+                                      float* grad, int32_t* status, int32_t* iters, const cave_sparse_cones* next_cones,
+                                      const cave_lite_store* next, int32_t* pack_status, uint32_t* cu_tickets, void* stream) {
+  return cone_step_sparse_impl(solve, ids, pred, B, CAVE_MODE_INNER_IPM, sign, 0.0f, max_iter, flags, proj, rnorm, target, loss,
+                               grad, status, iters, next_cones, next, pack_status, nullptr, nullptr, nullptr, cu_tickets, stream,
+                               true);
 }
 
 int32_t cave_hip_lite_from_packed(const cave_cone_store* src, const cave_lite_store* dst, int32_t* status, void* stream) {

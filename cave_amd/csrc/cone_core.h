@@ -2036,6 +2036,169 @@ template <class C>
 CAVE_HD SolveResult solve_cone_ipm(C& c, const SolveView& v, SolveWork& w, int steps) {
   return v.pm1 ? solve_cone_ipm_impl<C, true>(c, v, w, steps) : solve_cone_ipm_impl<C, false>(c, v, w, steps);
 }
+#if defined(CAVE_GPU_CODE)
+// ---- the interior-point steps on ONE wave over the lite index structures (step kernels, IPM variant: cone_step.h)
+// H = M diag(rho') M^T in full: the weights are continuous, so nothing of lite_hessian's incremental form (weights on
+// a grid of sixteenths, H += (w - w_old) m m^T for the few columns that moved) carries over.  The same column walk:
+// four coordinates per lane, one 16-byte index read per column, all lanes walk the (e1, e2 <= e1) pairs together and
+// stop at the longest column with a weight; lower triangle only (gj_solve<.., LOWER>).  Columns with rho' = 0 -- both
+// unit rows present, u == 3 -- add nothing and are skipped wave-uniformly.  The adds of one wave into LDS are ordered
+// by lane: the sums are the same on every run.
+template <class C>
+__device__ __forceinline__ void lite_hessian_ipm(C& c, const LiteCone& L, const SolveView& v, SolveWork& w) {
+  constexpr int KC = kLiteMaxD / 64;
+  const int lane = c.lane_id(), d = v.d, p = v.p, ldh = w.ldh;
+  float wk[KC];
+#pragma unroll
+  for (int s = 0; s < KC; ++s) {
+    const int k = lane + 64 * s;
+    wk[s] = w.wold[k < d ? k : d - 1];
+  }
+  for (int idx = lane; idx < p * ldh; idx += 64) w.H[idx] = 0.0;
+  c.sync();
+#pragma unroll
+  for (int s = 0; s < KC; ++s) {
+    if (64 * s >= d) continue;  // wave-uniform: no coordinate in this slot
+    const int k = lane + 64 * s;
+    const bool on = k < d && wk[s] > 0.0f;
+    if (__ballot(on) == 0ull) continue;  // wave-uniform
+    const double dw = (double)wk[s];
+    const uint4 t4 = *reinterpret_cast<const uint4*>(L.ell + 4 * (k < d ? k : d - 1));
+    const uint32_t cw[4] = {t4.x, t4.y, t4.z, t4.w};
+    static_for<0, 8>([&](auto e1c) {
+      constexpr int e1 = decltype(e1c)::value;
+      const uint32_t x1 = (cw[e1 >> 1] >> ((e1 & 1) * 16)) & 0xffffu;
+      const bool on1 = on && (x1 & 0x7fffu) != kLiteDummyRow;
+      if (e1 < L.cmax && __ballot(on1) != 0ull) {
+        const uint32_t a = x1 & 0x7fffu;
+        const double va = (x1 & 0x8000u) ? -dw : dw;
+        double* Ha = w.H + a * ldh;
+        if (on1) c.atomic_add_f64(Ha + a, dw);
+        static_for<0, e1>([&](auto e2c) {
+          constexpr int e2 = decltype(e2c)::value;
+          const uint32_t x2 = (cw[e2 >> 1] >> ((e2 & 1) * 16)) & 0xffffu;
+          if (on1) c.atomic_add_f64(Ha + (x2 & 0x7fffu), (x2 & 0x8000u) ? -va : va);
+        });
+      }
+    });
+  }
+  c.sync();
+}
+
+// solve_cone_ipm_impl<C, true> for a lite cone (p <= 32 reduced rows, rows ordered [free | bound]): the same constants
+// in the same order -- tau0 = 0.1 ymax^2, theta = z = sqrt(tau) on the bound rows, the smoothed residual by `usign`,
+// rhs = -g + tau / theta, z / theta on the diagonal, 0.995 to the boundary for both step lengths, tau <- 0.2 gap / nineq
+// with its floor -- so the iterates are those of the general kernels up to the order of the sums.  A step is one
+// lite_gather, one lite_gradient (rc[d] = 0 is its dummy coordinate), one lite_hessian_ipm and ONE register Gauss-Jordan
+// of all p rows (no fixed rows, no active-set loop, no line search).  Scratch: w.ttry = z, w.told = dz, w.wold = rho'.
+// A cone of unit rows only (p == 0) runs no step: its result is the smoothing of y at tau0, as in the general code.
+template <class C>
+__device__ __forceinline__ SolveResult lite_solve_ipm(C& c, const SolveView& v, SolveWork& w, int steps) {
+  const int NT = C::NT;
+  const int p = v.p, d = v.d, ldh = w.ldh, lane = c.lane_id();
+  const LiteCone& L = c.lite;
+  double* theta = w.theta;
+  double* r = w.res;
+  double* rc = w.rc;
+  float* wgt = w.wold;
+  double* z = w.ttry;
+  SolveResult out;
+  out.iters = 0;
+  out.status = ST_OK;
+  double yy = 0.0, ymax = 0.0;
+  for (int k = lane; k < d; k += NT) {
+    yy += (double)w.y[k] * (double)w.y[k];
+    ymax = fmax(ymax, fabs((double)w.y[k]));
+  }
+  yy = c.reduce_sum(yy);
+  ymax = c.reduce_max(ymax);
+  double tau = 0.1 * ymax * ymax;
+  if (!(tau > 0.0)) tau = 1e-300;
+  const double tau_min = fmax(1e-14 * ymax * ymax, 1e-300);
+  const bool mine = lane < p, bound = mine && !v.vkind[mine ? lane : 0];
+  if (mine) {
+    theta[lane] = bound ? sqrt(tau) : 0.0;
+    z[lane] = bound ? sqrt(tau) : 0.0;
+    w.act[lane] = 0;
+  }
+  const uint32_t nineq = c.reduce_add_u32(bound ? 1u : 0u);
+  c.sync();
+  auto residual = [&]() {  // r = y - M^T theta
+    if (p > 0) lite_gather(c, L, d, w.y, theta, -1.0, r);
+    else {
+      for (int k = lane; k < d; k += NT) r[k] = (double)w.y[k];
+      c.sync();
+    }
+  };
+  auto smooth_residual = [&](double t) {  // r -> rho (rc) and rho' (wgt); returns 1/2 ||rho||^2
+    double acc = 0.0;
+    for (int k = lane; k < d; k += NT) {
+      const uint8_t u = v.usign[k];
+      const double s = r[k];
+      const double q = sqrt(s * s + 4.0 * t);
+      double rho = s, dr = 1.0;
+      if (u == 1) { rho = 0.5 * (s - q); dr = 0.5 * (1.0 - s / q); }
+      else if (u == 2) { rho = 0.5 * (s + q); dr = 0.5 * (1.0 + s / q); }
+      else if (u == 3) { rho = 0.0; dr = 0.0; }
+      rc[k] = rho;
+      wgt[k] = (float)dr;
+      acc += rho * rho;
+    }
+    const double f = 0.5 * c.reduce_sum(acc);
+    c.sync();
+    return f;
+  };
+  int it = 0;
+  for (; it < steps && p > 0; ++it) {
+    residual();
+    smooth_residual(tau);
+    lite_gradient(c, L, p, rc, w.g);  // g = -M rho
+    lite_hessian_ipm(c, L, v, w);
+    if (mine) {
+      double rhs = -w.g[lane];
+      if (bound) {
+        const double inv = 1.0 / theta[lane];
+        rhs += tau * inv;
+        w.H[lane * ldh + lane] += z[lane] * inv;
+      }
+      w.g2[lane] = rhs;
+    }
+    c.sync();
+    gj_solve<32, true>(lane, w.H, ldh, w.g2, w.act, p, 1e-12, w.step);
+    c.sync();
+    double ap = 1e300, ad = 1e300, dz = 0.0;
+    if (bound) {
+      const double inv = 1.0 / theta[lane];
+      dz = tau * inv - z[lane] - z[lane] * inv * w.step[lane];
+      if (w.step[lane] < 0.0) ap = fmin(ap, -theta[lane] / w.step[lane]);
+      if (dz < 0.0) ad = fmin(ad, -z[lane] / dz);
+    }
+    if (mine) w.told[lane] = dz;
+    ap = -c.reduce_max(-ap);
+    ad = -c.reduce_max(-ad);
+    const double alpha_p = fmin(1.0, 0.995 * ap), alpha_d = fmin(1.0, 0.995 * ad);
+    double gap = 0.0;
+    if (mine) {
+      theta[lane] += alpha_p * w.step[lane];
+      z[lane] += alpha_d * w.told[lane];
+      gap = theta[lane] * z[lane];
+    }
+    gap = c.reduce_sum(gap);
+    tau = nineq > 0u ? 0.2 * gap / (double)nineq : 0.2 * tau;
+    if (!(tau > tau_min)) tau = tau_min;  // (the floor of solve_cone_ipm_impl)
+    c.sync();
+  }
+  residual();
+  const double f = smooth_residual(tau);
+  for (int k = lane; k < d; k += NT) r[k] = rc[k];
+  c.sync();
+  if (!(f == f) || !(yy == yy)) out.status = ST_BAD_INPUT;
+  out.f = f;
+  out.iters = it;
+  return out;
+}
+#endif  // CAVE_GPU_CODE
+
 // large-cone path (a real call, like solve_cone_band_call)
 template <class C>
 CAVE_NOINLINE void solve_cone_ipm_band_call(C& c_, const SolveView& v_, SolveWork& w_, int steps, SolveResult* out) {

@@ -407,7 +407,10 @@ CAVE_HD void run_lite_from_packed(C& c, unsigned char* smem, const LiteFromPacke
 // one memory round trip), run the one-wave Newton solver, fused epilogue.  `lane`: 0..63.
 // WARM: the multiplier cache W (StepWarm) is probed before the solve and written back after it; an instance that does not
 // hit runs exactly the cold instructions from the same state (w.warm = null).
-template <class SC, bool WARM = false>
+// IPM: the interior-point variant (k_step_ipm.hip, k_step_sparse_ipm.hip): the instance runs P.max_iter steps of
+// lite_solve_ipm (cone_core.h) instead of the Newton solver, for MODE_IPM only -- no cache, no average normal, none of
+// lite_model_step's scratch.  The cold and warm instantiations refuse that mode (CAVE_ST_TOO_LARGE) as before.
+template <class SC, bool WARM = false, bool IPM = false>
 CAVE_HD void run_lite_instance(SC& sc, unsigned char* smem, uint32_t lds_bytes, const StepSolveParams& P, int64_t b,
                                const StepWarm& W) {
   const cave_lite_store& S = P.store;
@@ -421,9 +424,10 @@ CAVE_HD void run_lite_instance(SC& sc, unsigned char* smem, uint32_t lds_bytes, 
   const int64_t slot_raw = P.ids ? P.ids[b] : b;
   const bool in_range = slot_raw >= 0 && slot_raw < S.n;
   const int64_t slot = in_range ? slot_raw : 0;
+  static_assert(!(WARM && IPM), "the interior iterate is not a starting point: the IPM variant has no cache");
   const int mode = P.mode;
-  const bool need_avg = (mode == MODE_INNER || mode == MODE_HEURISTIC || mode == MODE_AVG);
-  const bool need_proj = (mode == MODE_PROJECT || mode == MODE_EXACT || mode == MODE_INNER);
+  const bool need_avg = !IPM && (mode == MODE_INNER || mode == MODE_HEURISTIC || mode == MODE_AVG);
+  const bool need_proj = IPM || (mode == MODE_PROJECT || mode == MODE_EXACT || mode == MODE_INNER);
   // ---- prologue: EVERY global load of the instance in one memory round trip -- the header words beside the arrays
   // (nothing below depends on them: a slot's arrays have fixed extents, what a cone does not use is loaded and dropped);
   // until round 4 the header came first and the arrays a latency later (~2 us of a 70 us instance)
@@ -451,7 +455,9 @@ CAVE_HD void run_lite_instance(SC& sc, unsigned char* smem, uint32_t lds_bytes, 
   const int p = __builtin_amdgcn_readlane(hv, 1), nF = __builtin_amdgcn_readlane(hv, 3), n_valid = __builtin_amdgcn_readlane(hv, 4);
   const int cmax = __builtin_amdgcn_readlane(hv, 5), chn8 = __builtin_amdgcn_readlane(hv, 6);
   if (!in_range) st = ST_BAD_INPUT;
-  else if (state != 1 || p < 0 || p > kLiteMaxRows || chn8 > kLiteMaxChunk || mode == MODE_IPM) st = ST_TOO_LARGE;
+  // (the mode test is a ternary on the template constant: the front end folds it, and the cold and warm kernels keep the
+  //  instructions they had when the test read `mode == MODE_IPM`)
+  else if (state != 1 || p < 0 || p > kLiteMaxRows || chn8 > kLiteMaxChunk || (IPM ? mode != MODE_IPM : mode == MODE_IPM)) st = ST_TOO_LARGE;
   else {
     const uint32_t pp = (uint32_t)(p > 0 ? p : 1);
     float* y = ar.get<float>(d);
@@ -572,7 +578,7 @@ CAVE_HD void run_lite_instance(SC& sc, unsigned char* smem, uint32_t lds_bytes, 
       // scratch of lite_model_step: the epilogue's target vector (idle while the solver runs) when it is big enough,
       // else a block of its own (small cost dimensions: the arena is sized for d = 256)
       const int nI = p - nF;
-      const uint32_t need = lite_scratch_doubles(p, nI);
+      const uint32_t need = IPM ? 0u : lite_scratch_doubles(p, nI);
       double* scr = need <= (uint32_t)d ? w.q : ar.try_get<double>(need);
       // (warm: the hit's multipliers in LDS -- lane i < 32 stores theta_i and the solver's lane i reads it back: no sync --
       //  beyond the arena, or after every cold allocation: a miss sees the arena of the cold kernel; no room = a miss)
@@ -585,7 +591,8 @@ CAVE_HD void run_lite_instance(SC& sc, unsigned char* smem, uint32_t lds_bytes, 
       bool solved = false;
       if (need_proj && !empty && !scr) st = ST_TOO_LARGE;
       else if (need_proj && !empty) {
-        w.ls_on = true;
+        // (IPM: the interior-point steps need none of the active-set fields; they are set all the same, unread)
+        w.ls_on = !IPM;
         w.ls_nF = nF;
         w.ls_nI = nI;
         w.ls_scr = scr;
@@ -597,7 +604,9 @@ CAVE_HD void run_lite_instance(SC& sc, unsigned char* smem, uint32_t lds_bytes, 
 #ifdef CAVE_EMUL_COUNTERS
         if (lane == 0) ++emul_counters()[6];  // test builds: instances the solve half ran the lite solver for
 #endif
-        const SolveResult r = solve_cone_impl<SC, true, false>(sc, v, w, P.max_iter, 1e-11);
+        SolveResult r;
+        if constexpr (IPM) r = lite_solve_ipm(sc, v, w, P.max_iter);
+        else r = solve_cone_impl<SC, true, false>(sc, v, w, P.max_iter, 1e-11);
         st = r.status;
         f = r.f;
         iters = r.iters;

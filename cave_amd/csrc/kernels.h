@@ -241,7 +241,10 @@ __device__ __forceinline__ void step_release(uint32_t* masks, uint32_t claim) {
 // arenas of the cold kernel (P.W.lds_extra bytes at the end of the block are the warm solve's own)
 template <bool WARM> struct StepArg { using type = StepParams; };
 template <> struct StepArg<true> { using type = StepParamsWarm; };
-template <class CP, bool WARM = false>
+// IPM: the solve half runs the truncated interior-point steps of MODE_IPM (cone_step.h run_lite_instance<.., IPM>); the
+// pack half, the wave election and the pack priority are those of the cold kernel.  No tail priority: that raise is
+// keyed to Newton rounds, and every instance of this variant runs the same number of steps.
+template <class CP, bool WARM = false, bool IPM = false>
 __global__ __launch_bounds__(CP::NT, 2) void cone_step_kernel(typename StepArg<WARM>::type P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int64_t b = blockIdx.x;
@@ -264,7 +267,7 @@ __global__ __launch_bounds__(CP::NT, 2) void cone_step_kernel(typename StepArg<W
     sc.st = stamps;
     unsigned long long mt0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
 #endif
-    run_lite_instance<SoloCtx<32, 4>, WARM>(sc, smem + kStepElectBytes, lds_bytes - kStepElectBytes, P.S, b, W);
+    run_lite_instance<SoloCtx<32, 4>, WARM, IPM>(sc, smem + kStepElectBytes, lds_bytes - kStepElectBytes, P.S, b, W);
     if (sc.lane == 0) step_release(P.tickets, claim);
 #ifdef CAVE_STAMPS
     stamps[14] = __builtin_amdgcn_s_memtime() - mt0;
@@ -304,7 +307,7 @@ __global__ __launch_bounds__(CP::NT, 2) void cone_step_kernel(typename StepArg<W
 // stay as they are.
 template <bool WARM> struct StepSparseArg { using type = StepSparseParams; };
 template <> struct StepSparseArg<true> { using type = StepSparseParamsWarm; };
-template <class CP, bool WARM = false>
+template <class CP, bool WARM = false, bool IPM = false>
 __global__ __launch_bounds__(CP::NT, 2) void cone_step_sparse_kernel(typename StepSparseArg<WARM>::type P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int64_t b = blockIdx.x;
@@ -326,7 +329,7 @@ __global__ __launch_bounds__(CP::NT, 2) void cone_step_sparse_kernel(typename St
     for (int i = 0; i < 32; ++i) stamps[i] = 0;
     sc.st = stamps;
 #endif
-    run_lite_instance<SoloCtx<32, 4>, WARM>(sc, smem + kStepElectBytes, lds_bytes - kStepElectBytes, P.S, b, W);
+    run_lite_instance<SoloCtx<32, 4>, WARM, IPM>(sc, smem + kStepElectBytes, lds_bytes - kStepElectBytes, P.S, b, W);
     if (sc.lane == 0) step_release(P.tickets, claim);
     return;
   }
@@ -382,6 +385,8 @@ CAVE_DECL_LAUNCH(launch_step, StepParams);
 CAVE_DECL_LAUNCH(launch_step_warm, StepParamsWarm);
 CAVE_DECL_LAUNCH(launch_step_sparse, StepSparseParams);
 CAVE_DECL_LAUNCH(launch_step_sparse_warm, StepSparseParamsWarm);
+CAVE_DECL_LAUNCH(launch_step_ipm, StepParams);
+CAVE_DECL_LAUNCH(launch_step_sparse_ipm, StepSparseParams);
 CAVE_DECL_LAUNCH(launch_lite_from_packed, LiteFromPackedParams);
 
 template <class K>

@@ -486,13 +486,15 @@ class ConeStore:
                     _lib.ptr(out.get("loss")), _lib.ptr(out.get("grad")), _lib.ptr(status), _lib.ptr(iters),
                     _lib.current_stream())
                 _lib.check(rc, "cave_hip_cone_packed_large")
-            elif (self.lite_slots is not None and B <= 2048 and mode != _lib.MODE_INNER_IPM and self.waves == 0
-                  and (not self.warm_start or getattr(self, "lite_warm", None) is not None)):
+            elif (self.lite_slots is not None and B <= 2048 and self.waves == 0
+                  and (mode == _lib.MODE_INNER_IPM or not self.warm_start or getattr(self, "lite_warm", None) is not None)):
                 from .qpsolver import _launch_step
 
-                # (warm start: the multiplier cache keyed by store slot; out["warm_hit"] marks the instances that hit)
+                # (warm start: the multiplier cache keyed by store slot; out["warm_hit"] marks the instances that hit.
+                #  The interior-point mode has a kernel of its own and always runs cold: no cache, no "warm_hit")
+                warm = self.lite_warm if self.warm_start and mode != _lib.MODE_INNER_IPM else None
                 _launch_step(self.lite_slots, pred, B, mode, sign, inner_ratio, max_iter, out, status, iters, None, None, ids=ids,
-                             zero_failed=zero_failed, warm=self.lite_warm if self.warm_start else None, keys=ids)
+                             zero_failed=zero_failed, warm=warm, keys=ids)
                 if zero_failed:
                     out["zero_failed"] = True
             else:

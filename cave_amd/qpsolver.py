@@ -286,9 +286,18 @@ def _step_qualifies_sparse(x) -> bool:
 
 def _launch_step_sparse(solve, pred, B, mode, sign, inner_ratio, max_iter, out, status, iters, nxt_cones, nxt_store,
                         zero_failed=False, warm=None, keys=None):
-    """_launch_step with the next batch on the sparse wire format (cave_hip_cone_step_sparse)."""
+    """_launch_step with the next batch on the sparse wire format (cave_hip_cone_step_sparse; mode INNER_IPM:
+    cave_hip_cone_step_sparse_ipm, which has no cache -- `warm` is ignored, the mode runs cold)."""
     lib = _lib.load()
     dev = nxt_cones.device
+    if mode == _lib.MODE_INNER_IPM and B > 0:
+        rc = lib.cave_hip_cone_step_sparse_ipm(
+            solve.ref if solve is not None else None, None, _lib.ptr(pred), B, float(sign), int(max_iter), 1 if zero_failed else 0,
+            _lib.ptr(out.get("proj")), _lib.ptr(out.get("rnorm")), _lib.ptr(out.get("target")), _lib.ptr(out.get("loss")),
+            _lib.ptr(out.get("grad")), _lib.ptr(status), _lib.ptr(iters),
+            nxt_cones.c_ref(), nxt_store.ref, _lib.ptr(nxt_store.pack_status), _lib.ptr(_tickets_for(dev)), _lib.current_stream())
+        _lib.check(rc, "cave_hip_cone_step_sparse_ipm")
+        return
     hit = None
     if warm is not None and B > 0:
         hit = out["warm_hit"] = torch.empty(B, dtype=torch.uint8, device=dev)
@@ -306,10 +315,21 @@ def _launch_step(solve, pred, B, mode, sign, inner_ratio, max_iter, out, status,
                  zero_failed=False, warm=None, keys=None):
     """One launch of the step kernel.  `warm` (a cave_amd.warm.WarmCache): the warm variant, which starts each solve from
     the cache's multipliers for its key -- `keys` [B] int64, or None: the content of the cone -- and writes the
-    final ones back; out["warm_hit"] [B] uint8 then tells which instances hit."""
+    final ones back; out["warm_hit"] [B] uint8 then tells which instances hit.  Mode INNER_IPM goes to the kernel of
+    its own (cave_hip_cone_step_ipm), which has no cache: `warm` is ignored, the mode runs cold."""
     lib = _lib.load()
     Bn, mn, dn = (nxt_ctrs.shape if nxt_ctrs is not None else (0, 0, solve.d))
     dev = status.device if status is not None else nxt_ctrs.device
+    if mode == _lib.MODE_INNER_IPM and B > 0:
+        rc = lib.cave_hip_cone_step_ipm(
+            solve.ref if solve is not None else None, _lib.ptr(ids), _lib.ptr(pred), B, float(sign), int(max_iter),
+            1 if zero_failed else 0,
+            _lib.ptr(out.get("proj")), _lib.ptr(out.get("rnorm")), _lib.ptr(out.get("target")), _lib.ptr(out.get("loss")),
+            _lib.ptr(out.get("grad")), _lib.ptr(status), _lib.ptr(iters),
+            _lib.ptr(nxt_ctrs), Bn, mn, dn, nxt_store.ref if nxt_store is not None else None,
+            _lib.ptr(nxt_store.pack_status) if nxt_store is not None else None, _lib.ptr(_tickets_for(dev)), _lib.current_stream())
+        _lib.check(rc, "cave_hip_cone_step_ipm")
+        return
     args = (solve.ref if solve is not None else None, _lib.ptr(ids), _lib.ptr(pred), B, int(mode), float(sign), float(inner_ratio),
             int(max_iter), 1 if zero_failed else 0,
             _lib.ptr(out.get("proj")), _lib.ptr(out.get("rnorm")), _lib.ptr(out.get("target")), _lib.ptr(out.get("loss")),
@@ -369,7 +389,8 @@ def cone_op_prepared(prep: PreparedCones, pred_cost: torch.Tensor, mode: int, si
     form does not take falls back to the general operator of its own wire format, cone_op_dense or cone_op_sparse
     (checked calls only; unchecked calls report CAVE_ST_TOO_LARGE in `status`); an instance the sparse loader rejected
     reports CAVE_ST_BAD_INPUT.  `warm` (cave_amd.warm.WarmCache on this device) / `keys` ([B] int64 or None:
-    keyed by cone content): warm start from the cache, out["warm_hit"] says where it hit (the fallbacks run cold)."""
+    keyed by cone content): warm start from the cache, out["warm_hit"] says where it hit (the fallbacks run cold).
+    Mode INNER_IPM runs the interior-point step kernels (cave_hip_cone_step_ipm / _sparse_ipm), always cold."""
     _lib.load()
     B, m, d = prep.shape
     dev = prep.ctrs.device
@@ -379,8 +400,8 @@ def cone_op_prepared(prep: PreparedCones, pred_cost: torch.Tensor, mode: int, si
         return op(prep.ctrs, pred_cost, mode, sign, inner_ratio, max_iter=max_iter, check=chk, outputs=outputs)
 
     follow, prep.follow = prep.follow, None
-    if prep.stale() or mode == _lib.MODE_INNER_IPM:
-        # its store now holds a later batch (or the mode is not one of the step kernel's): solve from the batch itself
+    if prep.stale():
+        # its store now holds a later batch: solve from the batch itself
         if follow is not None:
             prep.next = prepare_cones(follow)
         return general(check)

@@ -397,6 +397,24 @@ int32_t cave_hip_cone_step_sparse(const cave_lite_store* solve, const int64_t* i
                                   const cave_warm_cache* warm, const int64_t* keys, uint8_t* warm_hit, uint32_t* cu_tickets,
                                   void* stream);
 
+/* ------------------------------------------------------------------ interior-point fused step (additive to v10)
+ * CAVE_MODE_INNER_IPM on the fused step: cave_hip_cone_step / cave_hip_cone_step_sparse without `mode`, `inner_ratio`
+ * and the cache arguments -- 22 and 19 parameters.  The solve half runs max_iter (<= 0: 3) interior-point steps per
+ * instance on one wave (the iterates of cave_hip_cone_dense in that mode, up to the order of the sums; `iters` = steps
+ * run, 0 for a cone without reduced rows) and the fused loss / gradient of the mode; always cold (the interior iterate
+ * is not a starting point).  Everything else -- the pack half and its limits, the stores, ids, B = 0 (pack only),
+ * B_next = 0 / next_cones == NULL (solve only), pack_status, CAVE_STEP_ZERO_FAILED, cu_tickets, the CAVE_E_INVALID
+ * cases -- is as for the sibling.  cave_hip_cone_step and cave_hip_cone_step_sparse keep refusing the mode. */
+int32_t cave_hip_cone_step_ipm(const cave_lite_store* solve, const int64_t* ids, const float* pred, int64_t B, float sign,
+                               int32_t max_iter, int32_t flags, float* proj, float* rnorm, float* target, float* loss,
+                               float* grad, int32_t* status, int32_t* iters, const float* next_ctrs, int64_t B_next,
+                               int64_t m_max, int64_t d, const cave_lite_store* next, int32_t* pack_status,
+                               uint32_t* cu_tickets, void* stream);
+int32_t cave_hip_cone_step_sparse_ipm(const cave_lite_store* solve, const int64_t* ids, const float* pred, int64_t B, float sign,
+                                      int32_t max_iter, int32_t flags, float* proj, float* rnorm, float* target, float* loss,
+                                      float* grad, int32_t* status, int32_t* iters, const cave_sparse_cones* next_cones,
+                                      const cave_lite_store* next, int32_t* pack_status, uint32_t* cu_tickets, void* stream);
+
 /* Device-resident stores: cones are static per instance (src/dataset.py:72), so a packed store whose cones qualify
  * builds the lite slots of ALL its instances once (slot i of `dst` from slot i of `src`, dst->n >= src->n) and then
  * serves batches of ids through the solve half of cave_hip_cone_step (no pack half).  status [src->n] or NULL:
