@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include "kernels.h"
+#include "sp_grid.h"
 
 namespace cave {
 
@@ -585,6 +586,38 @@ int32_t cave_hip_lite_from_packed(const cave_cone_store* src, const cave_lite_st
   P.src = *src; P.dst = *dst; P.n = src->n; P.lds_bytes = lds; P.status = status; P.lite_pmax = lite_pmax_table((int)src->d);
   hipError_t e = launch_lite_from_packed((unsigned)src->n, lds, (hipStream_t)stream, P);
   if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch lite_from_packed_kernel", e);
+  return CAVE_OK;
+}
+
+// ------------------------------------------------------------------ grid shortest path (sp_grid.h)
+
+int32_t cave_hip_sp_grid_lds_bytes(int64_t h, int64_t w) {
+  const uint32_t lds = sp_grid_wave_lds_bytes(h, w);
+  if (lds == 0u) return fail(CAVE_E_INVALID, "sp_grid_lds_bytes: need h, w >= 1, h*w >= 2 and an instance that fits the LDS");
+  return (int32_t)lds;
+}
+
+int32_t cave_hip_sp_grid_solve(const float* costs, const float* eval_costs, int64_t N, int64_t h, int64_t w, float* sol,
+                               double* obj, double* eval, int32_t* status, uint32_t* key, float* val, void* stream) {
+  if (h < 1 || w < 1 || h * w < 2) return fail(CAVE_E_INVALID, "sp_grid_solve: bad shape (need h, w >= 1 and h*w >= 2)");
+  const uint32_t wave_lds = sp_grid_wave_lds_bytes(h, w);
+  if (wave_lds == 0u) return fail(CAVE_E_INVALID, "sp_grid_solve: the grid does not fit the LDS (cave_hip_sp_grid_lds_bytes)");
+  const int64_t d = sp_grid_arcs(h, w);
+  if ((key == nullptr) != (val == nullptr)) return fail(CAVE_E_INVALID, "sp_grid_solve: key and val go together");
+  if (key && (d > 65535 || 2 * h * w + d > 65535))
+    return fail(CAVE_E_INVALID, "sp_grid_solve: cone output needs d <= 65535 and 2*h*w + d <= 65535 (16-bit rows and columns)");
+  if (eval && !eval_costs) return fail(CAVE_E_INVALID, "sp_grid_solve: eval needs eval_costs");
+  if (N < 0) return fail(CAVE_E_INVALID, "sp_grid_solve: bad N");
+  if (N == 0) return CAVE_OK;
+  if (!costs) return fail(CAVE_E_INVALID, "sp_grid_solve: costs is null");
+  const int waves = sp_grid_waves(wave_lds);
+  const int64_t grid = (N + waves - 1) / waves;
+  if (grid >= (int64_t)1 << 31) return fail(CAVE_E_INVALID, "sp_grid_solve: batch too large");
+  SpGridParams P;
+  P.costs = costs; P.eval_costs = eval_costs; P.N = N; P.h = (int32_t)h; P.w = (int32_t)w; P.d = (int32_t)d;
+  P.wave_lds = wave_lds; P.sol = sol; P.obj = obj; P.eval = eval; P.status = status; P.key = key; P.val = val;
+  hipError_t e = launch_sp_grid((unsigned)grid, waves, (hipStream_t)stream, P);
+  if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch sp_grid_kernel", e);
   return CAVE_OK;
 }
 

@@ -135,6 +135,16 @@ class SparseCones:
         return cls._from_parts(parts, d, m_max)
 
     @classmethod
+    def from_uniform(cls, m_max: int, d: int, nnz: int, key: torch.Tensor, val: torch.Tensor) -> "SparseCones":
+        """A batch whose instances all hold `nnz` entries, from canonical flat key / val tensors (what a device kernel
+        writes: cave_amd.tight.sp_cones_hip); ent_off is made on their device, nothing is copied or checked."""
+        nnz = int(nnz)
+        if nnz <= 0 or key.numel() % nnz:
+            raise ValueError("SparseCones.from_uniform: key must hold a whole number of instances")
+        off = torch.arange(key.numel() // nnz + 1, dtype=torch.int64, device=key.device) * nnz
+        return cls(m_max, d, off, key, val)
+
+    @classmethod
     def cat(cls, pieces, m_max: int | None = None) -> "SparseCones":
         """Concatenate batches (offset arithmetic only)."""
         pieces = list(pieces)

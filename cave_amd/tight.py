@@ -15,6 +15,12 @@ program and every rule of `_extract_tight_normals` can be applied without a solv
 This is the "next" row f2 of SURVEY.md §8 and lets BASELINE configs[0] (SP 5x5, 100 instances,
 batch 32) run end to end without Gurobi/PyEPO.  Host-side numpy; nothing here is on the hot path.
 
+The same dynamic program, the backtrack, the regret numerator and the tight cone in the sparse wire format also run on
+the device, one wave per instance (`sp_solve_hip`, `sp_cones_hip`; cave_amd/csrc/sp_grid.h): the additions and
+comparisons of `sp_solve` in `sp_solve`'s order, so paths and objectives are equal bit for bit, and the entries
+`SparseCones.from_ragged([sp_tight_normals(...)])` would hold, without the dense matrix.  `SPConeDataset(...,
+device=...)` and `sp_regret(..., device=...)` use them; without a device both do what they always did.
+
 Small TSP (DFJ model, src/model/tsp.py:54-60): the optimal tour comes from the Held-Karp dynamic program
 (`tsp_solve`, exact, O(n^2 2^n), n <= 14); the subtour-elimination rows come from the SAME lazy rule the
 reference's callback applies (first edge that closes a cycle in union-find order -> the cut of its component,
@@ -31,7 +37,7 @@ import numpy as np
 
 from .synth import sp_arcs
 
-__all__ = ["sp_solve", "sp_tight_normals", "sp_gen_data", "SPConeDataset", "sp_regret",
+__all__ = ["sp_solve", "sp_tight_normals", "sp_gen_data", "SPConeDataset", "sp_regret", "sp_solve_hip", "sp_cones_hip",
            "tsp_solve", "tsp_dfj_cuts", "tsp_tight_normals", "tsp_gen_data", "TSPConeDataset", "tsp_regret"]
 
 
@@ -87,14 +93,82 @@ def sp_gen_data(num_data: int, num_feat: int, h: int, w: int, deg: int = 4, nois
     return x.astype(np.float32), c.astype(np.float32)
 
 
+def _sp_grid_call(costs, h: int, w: int, eval_costs=None, cones: bool = False):
+    """One launch of cave_hip_sp_grid_solve on a (N, d) float32 device tensor -> (sols, objs, evals or None, key, val)."""
+    import torch
+
+    from . import _lib
+
+    lib = _lib.load()
+    h, w = int(h), int(w)
+    d = h * (w - 1) + (h - 1) * w
+    if not (isinstance(costs, torch.Tensor) and costs.is_cuda and costs.dtype == torch.float32 and costs.dim() == 2):
+        raise ValueError("sp_solve_hip: costs must be a (N, d) float32 tensor on the device")
+    if costs.shape[1] != d:
+        raise ValueError(f"sp_solve_hip: a {h} x {w} grid has {d} arcs, costs has {costs.shape[1]} columns")
+    costs = costs.contiguous()
+    if eval_costs is not None:
+        if not (isinstance(eval_costs, torch.Tensor) and eval_costs.dtype == torch.float32 and eval_costs.shape == costs.shape
+                and eval_costs.device == costs.device):
+            raise ValueError("sp_solve_hip: eval_costs must match costs in shape, dtype and device")
+        eval_costs = eval_costs.contiguous()
+    N, dev = costs.shape[0], costs.device
+    sols = torch.empty(N, d, dtype=torch.float32, device=dev)
+    objs = torch.empty(N, dtype=torch.float64, device=dev)
+    evals = torch.empty(N, dtype=torch.float64, device=dev) if eval_costs is not None else None
+    status = torch.empty(N, dtype=torch.int32, device=dev)
+    key = torch.empty(N * 5 * d, dtype=torch.int32, device=dev) if cones else None
+    val = torch.empty(N * 5 * d, dtype=torch.float32, device=dev) if cones else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.cave_hip_sp_grid_solve(_lib.ptr(costs), _lib.ptr(eval_costs), N, h, w, _lib.ptr(sols), _lib.ptr(objs),
+                                              _lib.ptr(evals), _lib.ptr(status), _lib.ptr(key), _lib.ptr(val),
+                                              _lib.current_stream()), "cave_hip_sp_grid_solve")
+    if N and bool((status != _lib.ST_OK).any()):
+        b = int(torch.nonzero(status != _lib.ST_OK)[0])
+        raise ValueError(f"sp_solve_hip: instance {b} has a non-finite cost")
+    return sols, objs, evals, key, val
+
+
+def sp_solve_hip(costs, h: int, w: int, eval_costs=None):
+    """`sp_solve` for a batch on the device: costs (N, d) float32 -> (sols (N, d) float32 0/1, objs (N,) float64), equal
+    to the host's bit for bit.  With `eval_costs` (N, d) a third result: evals (N,) float64, each path priced under the
+    second cost tensor (the regret numerator).  A non-finite cost raises ValueError."""
+    sols, objs, evals, _, _ = _sp_grid_call(costs, h, w, eval_costs)
+    return (sols, objs) if eval_costs is None else (sols, objs, evals)
+
+
+def sp_cones_hip(costs, h: int, w: int):
+    """Solve and, in the same launch, write the tight cones of the optimal vertices in the sparse wire format ->
+    (SparseCones on the device, sols, objs): the tensors `SparseCones.from_ragged([sp_tight_normals(s, h, w) for s in
+    sols])` holds, without a dense matrix or a host round trip.  Needs 2 h w + d <= 65535."""
+    from .sparse import SparseCones
+
+    sols, objs, _, key, val = _sp_grid_call(costs, h, w, None, cones=True)
+    d = sols.shape[1]
+    return SparseCones.from_uniform(2 * h * w + d, d, 5 * d, key, val), sols, objs
+
+
 class SPConeDataset:
     """`optDatasetConstrs` (src/dataset.py:26-130) for the grid shortest path, without Gurobi:
-    feats, costs, sols, objs and the ragged list of tight-constraint normals `ctrs`."""
+    feats, costs, sols, objs and the ragged list of tight-constraint normals `ctrs`.
 
-    def __init__(self, feats: np.ndarray, costs: np.ndarray, h: int, w: int):
+    With `device`: solved on the device in one launch (`sp_cones_hip`); feats, costs, sols and objs live there, there is
+    no dense `ctrs` list, `.cones` is the SparseCones of the whole set on the device and item i carries its one-instance
+    slice (views, no copy) -- what `collate_sparse`, `ConeStore.from_sparse(dataset.cones)` and `prefetch` take."""
+
+    def __init__(self, feats: np.ndarray, costs: np.ndarray, h: int, w: int, device=None):
         import torch
 
         self.h, self.w = h, w
+        self.cones = None
+        if device is not None:
+            device = torch.device(device)
+            self.feats = torch.as_tensor(feats, dtype=torch.float32).to(device)
+            self.costs = torch.as_tensor(costs, dtype=torch.float32).to(device)
+            self.cones, self.sols, objs = sp_cones_hip(self.costs, h, w)
+            self.objs = objs.to(torch.float32)[:, None]
+            self._off1 = self.cones.ent_off[:2]
+            return
         sols, objs, ctrs = [], [], []
         for c in costs:
             s, o = sp_solve(c, h, w)
@@ -111,11 +185,30 @@ class SPConeDataset:
         return len(self.feats)
 
     def __getitem__(self, i: int):
+        if self.cones is not None:
+            from .sparse import SparseCones
+
+            i = int(i) % len(self)
+            z = 5 * self.cones.d  # entries per instance
+            cone = SparseCones(self.cones.m_max, self.cones.d, self._off1, self.cones.key[i * z:(i + 1) * z],
+                               self.cones.val[i * z:(i + 1) * z])
+            return self.feats[i], self.costs[i], self.sols[i], self.objs[i], cone
         return self.feats[i], self.costs[i], self.sols[i], self.objs[i], self.ctrs[i]
 
 
-def sp_regret(pred_costs: np.ndarray, true_costs: np.ndarray, true_objs: np.ndarray, h: int, w: int) -> float:
-    """Normalised regret sum(c . w(c_hat) - z*) / sum(z*) (PyEPO `metric.regret` for a MIN problem)."""
+def sp_regret(pred_costs: np.ndarray, true_costs: np.ndarray, true_objs: np.ndarray, h: int, w: int, device=None) -> float:
+    """Normalised regret sum(c . w(c_hat) - z*) / sum(z*) (PyEPO `metric.regret` for a MIN problem).
+
+    With `device`: arrays or tensors, moved to the device if they are not there; solved and priced there in one launch
+    (fp64 sums), only the scalar comes back."""
+    if device is not None:
+        import torch
+
+        device = torch.device(device)
+        cp, c, z = (torch.as_tensor(t).detach().to(device=device, dtype=torch.float32) for t in (pred_costs, true_costs, true_objs))
+        _, _, evals = sp_solve_hip(cp, h, w, eval_costs=c)
+        z = z.reshape(-1).to(torch.float64)
+        return float(((evals - z).sum() / (z.abs().sum() + 1e-7)).item())
     loss = 0.0
     for cp, c, z in zip(pred_costs, true_costs, true_objs):
         s, _ = sp_solve(cp, h, w)

@@ -11,6 +11,7 @@ BASELINE configs[0] sizes (5x5 grid, 100 instances, batch 32); `--problem tsp` i
     python examples/train_sp_cave.py --problem tsp --prefetch  # dense cones: the next batch's pack rides in this batch's loss call
     python examples/train_sp_cave.py --sparse [--packed]       # cones on the sparse wire format: no dense padding anywhere
     python examples/train_sp_cave.py --problem tsp --sparse --prefetch [--warm-start]  # the fused step packs the next SPARSE batch
+    python examples/train_sp_cave.py --grid 30 30 --num-data 1000 --device-data --packed --inner ipm  # SP solved, cones built and regret evaluated on the device
 """
 
 import argparse
@@ -55,7 +56,13 @@ def main(argv=None):
                     help="the dataset hands out cones on the sparse wire format (cave_amd.sparse.SparseCones) and the loader "
                          "collates them with collate_sparse; with --packed the store is built by ConeStore.from_sparse")
     ap.add_argument("--lazy-check", action="store_true", help="solver_kwargs check='lazy': no host sync per step")
+    ap.add_argument("--device-data", action="store_true",
+                    help="(shortest path, with --packed or --sparse) solve the instances, build their tight cones on the sparse "
+                         "wire format and evaluate the regret on the device (SPConeDataset(..., device=), sp_regret(..., "
+                         "device=)): no dense cone is ever made")
     args = ap.parse_args(argv)
+    if args.device_data and (args.problem != "sp" or not (args.packed or args.sparse)):
+        ap.error("--device-data is for the shortest-path problem and needs --packed or --sparse (there are no dense cones)")
     if args.graph and (not args.packed or args.variant == "hybrid"):
         ap.error("--graph needs --packed and a variant without a per-call branch draw")
 
@@ -72,7 +79,7 @@ def main(argv=None):
         print(f"TSP-{args.nodes}: {len(dataset)} instances, {sum(dataset.tight_cuts)} tight subtour cuts in all")
     else:
         feats, costs = sp_gen_data(args.num_data, args.num_feat, h, w, deg=4, noise_width=0.5, seed=135)
-        dataset = SPConeDataset(feats, costs, h, w)
+        dataset = SPConeDataset(feats, costs, h, w, device="cuda" if args.device_data else None)
     dev = torch.device("cuda")
 
     class _Model:  # what the loss modules read from a PyEPO optModel
@@ -95,9 +102,12 @@ def main(argv=None):
         cave = innerConeAlignedCosine(_Model(), solver="hip", solve_ratio=0.3, inner_ratio=0.2, seed=0, solver_kwargs=kw or None)
 
     # --sparse: what a dataset built from a solver's sparse constraint matrix would keep -- one SparseCones per instance
-    sparse_ctrs = SparseCones.from_ragged(dataset.ctrs) if args.sparse else None
+    if args.device_data:
+        sparse_ctrs = dataset.cones   # already on the device, straight from the solve kernel
+    else:
+        sparse_ctrs = SparseCones.from_ragged(dataset.ctrs) if args.sparse else None
     if args.packed:
-        store = ConeStore.from_sparse(sparse_ctrs) if args.sparse else ConeStore.from_ragged(dataset.ctrs)
+        store = ConeStore.from_sparse(sparse_ctrs) if sparse_ctrs is not None else ConeStore.from_ragged(dataset.ctrs)
     else:
         store = None
     if store is not None and args.warm_start:
@@ -105,9 +115,11 @@ def main(argv=None):
 
     def collate(batch):  # reference collate_fn (src/dataset.py:133-144) / its id-returning replacement
         idx = torch.as_tensor(batch, dtype=torch.int64)
-        x, c = dataset.feats[idx], dataset.costs[idx]
+        x, c = dataset.feats[idx.to(dataset.feats.device)], dataset.costs[idx.to(dataset.costs.device)]
         if args.packed:
             return x, c, idx
+        if args.device_data:
+            return x, c, sparse_ctrs[idx]   # one gather on the device
         if args.sparse:
             return collate_sparse([(x[j], c[j], sparse_ctrs[i]) for j, i in enumerate(batch)])
         return x, c, pad_sequence([dataset.ctrs[i] for i in batch], batch_first=True, padding_value=0.0)
@@ -164,6 +176,9 @@ def main(argv=None):
                                 generator=torch.Generator().manual_seed(0))  # the same batch order as an eager run
 
     def regret():
+        if args.device_data:  # predictions and true costs stay on the device, only the scalar comes back
+            with torch.no_grad():
+                return sp_regret(reg(dataset.feats), dataset.costs, dataset.objs[:, 0], h, w, device=dev)
         with torch.no_grad():
             cp = reg(dataset.feats.to(dev)).cpu().numpy()
         if args.problem == "tsp":

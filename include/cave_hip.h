@@ -421,6 +421,30 @@ int32_t cave_hip_cone_step_sparse_ipm(const cave_lite_store* solve, const int64_
  * CAVE_ST_OK, or CAVE_ST_TOO_LARGE for a cone the one-wave solver does not take (its slot is marked so). */
 int32_t cave_hip_lite_from_packed(const cave_cone_store* src, const cave_lite_store* dst, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------ grid shortest path (additive to v10)
+ * The h x w grid DAG of PyEPO's shortest-path model (arcs go right or down; arc order: per grid row its w-1 right arcs,
+ * then its w down arcs; d = h (w-1) + (h-1) w), N instances, one wave each, in ONE launch:
+ *   costs      [N, d] fp32   the costs the path is optimal for
+ *   eval_costs [N, d] fp32   or NULL: a second cost tensor the path is priced under (the regret numerator)
+ *   sol        [N, d] fp32   or NULL: 0/1 arc indicator of the shortest source->sink path
+ *   obj        [N]    fp64   or NULL: its length under `costs`
+ *   eval       [N]    fp64   or NULL: sum_k eval_costs[b, k] sol[b, k] in fp64 (needs eval_costs)
+ *   status     [N]           or NULL: CAVE_ST_OK, or CAVE_ST_BAD_INPUT for a non-finite cost (zero sol, NaN obj / eval;
+ *                            the other instances are unaffected)
+ *   key, val   [N, 5 d]      or both NULL: the tight cone of each vertex on the sparse wire format -- rows
+ *                            [A; -A; -e_k for arcs at 0; +e_k for arcs at 1] with A the node-arc matrix (+1 head, -1
+ *                            tail), 2 h w + d rows and exactly 5 d entries per instance, so
+ *                            ent_off[b] = 5 d b, m_max = 2 h w + d (a bad instance gets the cone of the zero vector)
+ * Distances are fp64 sums of the fp32 costs along the path, a candidate replaces a distance only when strictly
+ * smaller, arcs in index order (at a tie the down arc into a node wins): paths and objectives do not depend on the
+ * batch, the launch or the device.  No workspace, no state between calls.  N == 0: nothing to do, CAVE_OK.
+ * CAVE_E_INVALID before any launch: h or w < 1, h w < 2; a grid whose instance does not fit the LDS (the size query
+ * below is negative); with key / val, d > 65535 or 2 h w + d > 65535; key without val; eval without eval_costs.
+ * The size query returns the LDS bytes one instance needs (at most 163840), or CAVE_E_INVALID. */
+int32_t cave_hip_sp_grid_lds_bytes(int64_t h, int64_t w);
+int32_t cave_hip_sp_grid_solve(const float* costs, const float* eval_costs, int64_t N, int64_t h, int64_t w, float* sol,
+                               double* obj, double* eval, int32_t* status, uint32_t* key, float* val, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
