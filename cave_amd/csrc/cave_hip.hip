@@ -9,6 +9,7 @@
 
 #include "kernels.h"
 #include "sp_grid.h"
+#include "tsp_hk.h"
 
 namespace cave {
 
@@ -618,6 +619,41 @@ int32_t cave_hip_sp_grid_solve(const float* costs, const float* eval_costs, int6
   P.wave_lds = wave_lds; P.sol = sol; P.obj = obj; P.eval = eval; P.status = status; P.key = key; P.val = val;
   hipError_t e = launch_sp_grid((unsigned)grid, waves, (hipStream_t)stream, P);
   if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch sp_grid_kernel", e);
+  return CAVE_OK;
+}
+
+// ------------------------------------------------------------------ Held-Karp TSP (tsp_hk.h)
+
+int64_t cave_hip_tsp_hk_slot_bytes(int64_t n) {
+  if (!tsp_hk_valid_n(n)) return fail(CAVE_E_INVALID, "tsp_hk_slot_bytes: need 3 <= n <= 14");
+  return tsp_hk_slot_bytes(n);
+}
+
+int64_t cave_hip_tsp_hk_workspace_bytes(int64_t n, int64_t N) {
+  if (!tsp_hk_valid_n(n) || N < 0) return fail(CAVE_E_INVALID, "tsp_hk_workspace_bytes: need 3 <= n <= 14 and N >= 0");
+  return tsp_hk_slot_bytes(n) * (N < kTspHkDefaultSlots ? N : kTspHkDefaultSlots);
+}
+
+int32_t cave_hip_tsp_hk_solve(const float* costs, const float* eval_costs, int64_t N, int64_t n, float* sol, double* obj,
+                              double* eval, int32_t* tour, int32_t* status, void* workspace, int64_t workspace_bytes,
+                              void* stream) {
+  if (!tsp_hk_valid_n(n)) return fail(CAVE_E_INVALID, "tsp_hk_solve: need 3 <= n <= 14");
+  if (eval && !eval_costs) return fail(CAVE_E_INVALID, "tsp_hk_solve: eval needs eval_costs");
+  if (N < 0) return fail(CAVE_E_INVALID, "tsp_hk_solve: bad N");
+  if (N == 0) return CAVE_OK;
+  const int64_t slot = tsp_hk_slot_bytes(n);
+  if (slot > 0 && (!workspace || workspace_bytes < slot || ((uintptr_t)workspace & 7u) != 0u))
+    return fail(CAVE_E_INVALID, "tsp_hk_solve: this n needs an 8-byte aligned workspace of at least one slot (cave_hip_tsp_hk_slot_bytes)");
+  if (!costs) return fail(CAVE_E_INVALID, "tsp_hk_solve: costs is null");
+  int64_t grid = slot > 0 ? workspace_bytes / slot : kTspHkLdsGrid;
+  if (grid > N) grid = N;
+  if (grid > ((int64_t)1 << 20)) grid = (int64_t)1 << 20;
+  TspHkParams P;
+  P.costs = costs; P.eval_costs = eval_costs; P.N = N; P.n = (int32_t)n; P.d = (int32_t)tsp_hk_edges(n);
+  P.sol = sol; P.obj = obj; P.eval = eval; P.tour = tour; P.status = status;
+  P.ws = slot > 0 ? static_cast<double*>(workspace) : nullptr; P.slot_doubles = slot / 8;
+  hipError_t e = launch_tsp_hk((unsigned)grid, (hipStream_t)stream, P);
+  if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch tsp_hk kernel", e);
   return CAVE_OK;
 }
 

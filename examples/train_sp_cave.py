@@ -12,6 +12,7 @@ BASELINE configs[0] sizes (5x5 grid, 100 instances, batch 32); `--problem tsp` i
     python examples/train_sp_cave.py --sparse [--packed]       # cones on the sparse wire format: no dense padding anywhere
     python examples/train_sp_cave.py --problem tsp --sparse --prefetch [--warm-start]  # the fused step packs the next SPARSE batch
     python examples/train_sp_cave.py --grid 30 30 --num-data 1000 --device-data --packed --inner ipm  # SP solved, cones built and regret evaluated on the device
+    python examples/train_sp_cave.py --problem tsp --nodes 12 --packed --device-regret  # the regret's Held-Karp solves run on the device
 """
 
 import argparse
@@ -60,6 +61,10 @@ def main(argv=None):
                     help="(shortest path, with --packed or --sparse) solve the instances, build their tight cones on the sparse "
                          "wire format and evaluate the regret on the device (SPConeDataset(..., device=), sp_regret(..., "
                          "device=)): no dense cone is ever made")
+    ap.add_argument("--device-regret", action="store_true",
+                    help="evaluate the regret on the device (tsp_regret(..., device=) / sp_regret(..., device=)): one launch "
+                         "solves every prediction and prices it, only the scalar comes back; the dataset and the training "
+                         "loop are untouched")
     args = ap.parse_args(argv)
     if args.device_data and (args.problem != "sp" or not (args.packed or args.sparse)):
         ap.error("--device-data is for the shortest-path problem and needs --packed or --sparse (there are no dense cones)")
@@ -179,6 +184,12 @@ def main(argv=None):
         if args.device_data:  # predictions and true costs stay on the device, only the scalar comes back
             with torch.no_grad():
                 return sp_regret(reg(dataset.feats), dataset.costs, dataset.objs[:, 0], h, w, device=dev)
+        if args.device_regret:  # a host dataset: costs and objectives go to the device, the predictions are there already
+            with torch.no_grad():
+                cp = reg(dataset.feats.to(dev))
+                if args.problem == "tsp":
+                    return tsp_regret(cp, dataset.costs, dataset.objs[:, 0], args.nodes, device=dev)
+                return sp_regret(cp, dataset.costs, dataset.objs[:, 0], h, w, device=dev)
         with torch.no_grad():
             cp = reg(dataset.feats.to(dev)).cpu().numpy()
         if args.problem == "tsp":

@@ -445,6 +445,38 @@ int32_t cave_hip_sp_grid_lds_bytes(int64_t h, int64_t w);
 int32_t cave_hip_sp_grid_solve(const float* costs, const float* eval_costs, int64_t N, int64_t h, int64_t w, float* sol,
                                double* obj, double* eval, int32_t* status, uint32_t* key, float* val, void* stream);
 
+/* ------------------------------------------------------------------ Held-Karp TSP (additive to v10)
+ * The symmetric TSP on n nodes, 3 <= n <= 14 (edges in lexicographic (i<j) order, d = n (n-1) / 2,
+ * eid(i,j) = i n - i (i+1) / 2 + j - i - 1), N instances, one 256-thread workgroup each, in ONE launch:
+ *   costs      [N, d] fp32   the costs the tour is optimal for
+ *   eval_costs [N, d] fp32   or NULL: a second cost tensor the tour is priced under (the regret numerator)
+ *   sol        [N, d] fp32   or NULL: 0/1 edge indicator of the optimal tour
+ *   obj        [N]    fp64   or NULL: its length under `costs`
+ *   eval       [N]    fp64   or NULL: the fp64 sum of eval_costs[b, eid(t_i, t_i+1)] over the tour's n edges in tour order,
+ *                            left to right, the closing edge last (needs eval_costs)
+ *   tour       [N, n] int32  or NULL: the tour, starting at node 0
+ *   status     [N]           or NULL: CAVE_ST_OK, or CAVE_ST_BAD_INPUT for a non-finite cost (zero sol, NaN obj / eval, a
+ *                            tour of -1; the other instances are unaffected)
+ *   workspace                n <= 12: unused, may be NULL (the table of the dynamic program lies in LDS).  n = 13, 14: a
+ *                            device buffer of workspace_bytes bytes, 8-byte aligned, at least one slot; the launch uses
+ *                            min(N, workspace_bytes / slot_bytes) workgroups, which stride over the instances, each
+ *                            keeping its table, (n-1) 2^(n-2) doubles, in its own slot.  Its contents on entry do not
+ *                            matter and mean nothing afterwards.
+ * The Held-Karp recurrence in fp64 on the exactly converted fp32 costs: one addition per candidate, candidates in
+ * ascending node order, a candidate replaces the minimum only when strictly smaller (the lowest node wins a tie), the
+ * closing edge likewise: tours and objectives do not depend on the batch, the launch, the workspace size or the device.
+ * No state between calls.  N == 0: nothing to do, CAVE_OK (no workspace needed).
+ * CAVE_E_INVALID before any launch: n < 3 or n > 14; eval without eval_costs; for n = 13, 14 and N > 0 a NULL or
+ * misaligned workspace or one smaller than one slot.
+ * cave_hip_tsp_hk_slot_bytes: 0 where the table lies in LDS (n <= 12), else the bytes of one slot (196608, 425984).
+ * cave_hip_tsp_hk_workspace_bytes: slot_bytes * min(N, 512), the default workspace (0 for n <= 12).  Both return
+ * CAVE_E_INVALID for an n out of range (the second also for N < 0). */
+int64_t cave_hip_tsp_hk_slot_bytes(int64_t n);
+int64_t cave_hip_tsp_hk_workspace_bytes(int64_t n, int64_t N);
+int32_t cave_hip_tsp_hk_solve(const float* costs, const float* eval_costs, int64_t N, int64_t n, float* sol, double* obj,
+                              double* eval, int32_t* tour, int32_t* status, void* workspace, int64_t workspace_bytes,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif
