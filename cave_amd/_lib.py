@@ -98,6 +98,35 @@ class Store(C.Structure):
     ]
 
 
+# The arrays of a cave_cone_store behind its two offset arrays: (field, element type, extent).  Extents: "n" one per
+# instance, "nd" one per cost coordinate, "nd1" the d + 1 CSC column pointers of an instance, "R" one per reduced row
+# (row_off[n]), "Z" one per non-zero (nnz_off[n]); an empty store keeps one dummy entry in the R and Z arrays.
+# int32 / int16 stand in for the header's uint32_t / uint16_t (torch has no unsigned types of those widths).
+STORE_ARRAYS = (
+    ("n_valid", "int32", "n"), ("flags", "uint8", "n"), ("usign", "uint8", "nd"), ("avg", "float32", "nd"),
+    ("vkind", "uint8", "R"), ("rlo", "int32", "R"), ("rhi", "int32", "R"), ("ccol", "int16", "Z"), ("cval", "float32", "Z"),
+    ("cptr", "int32", "nd1"), ("cvar", "int16", "Z"), ("cvalc", "float32", "Z"),
+)
+
+
+def alloc_store(device, d: int, row_off, nnz_off, R: int, Z: int, slot_mode: bool = False):
+    """Allocate (zeroed) the arrays of a cave_cone_store of n = len(row_off) - 1 instances on `device` and fill the
+    struct: -> (dict of tensors by field name, Store).  Exact-fit form: `row_off` / `nnz_off` [n+1] int64 are the prefix
+    sums of the count pass, R / Z their last entries, n_rows / n_nnz stay NULL.  Slot form (`slot_mode`): the offsets
+    give slot i its capacity window (i * rows, i * nnz) and n_rows / n_nnz [n] are allocated for the actual sizes."""
+    import torch
+
+    n = int(row_off.numel()) - 1
+    extent = {"n": n, "nd": n * d, "nd1": n * (d + 1), "R": max(R, 1), "Z": max(Z, 1)}
+    t = {"row_off": row_off, "nnz_off": nnz_off}
+    for name, dtype, ext in STORE_ARRAYS:
+        t[name] = torch.zeros(extent[ext], dtype=getattr(torch, dtype), device=device)
+    if slot_mode:
+        t["n_rows"] = torch.zeros(n, dtype=torch.int32, device=device)
+        t["n_nnz"] = torch.zeros(n, dtype=torch.int32, device=device)
+    return t, Store(n=n, d=d, reserved=0, **{k: v.data_ptr() for k, v in t.items()})
+
+
 class LiteStore(C.Structure):
     """struct cave_lite_store (include/cave_hip.h): transient per-batch store of the fused step kernel."""
     _fields_ = [

@@ -23,8 +23,8 @@ import torch
 from . import _lib
 from .abcmodule import EPO, optModule, sense_sign
 from .dataset import PackedBatch
-from .qpsolver import (PreparedCones, _step_qualifies, _step_qualifies_sparse, cone_op_dense, cone_op_prepared, cone_op_sparse,
-                       prepare_cones, prepare_dense, prepare_sparse)
+from .qpsolver import (PreparedCones, _step_qualifies, cone_op_dense, cone_op_prepared, cone_op_sparse, prepare_cones,
+                       prepare_dense, prepare_sparse)
 from .sparse import SparseCones
 from .warm import DEFAULT_ENTRIES, WarmCache
 
@@ -164,7 +164,7 @@ class _ConeLossFunction(torch.autograd.Function):
         if warm is not None and isinstance(tight_ctrs, SparseCones):
             # warm start on a plain sparse batch: the split form of the fused step (pack-only launch, then the warm solve);
             # a shape the step does not take runs cold on today's route
-            if _step_qualifies_sparse(tight_ctrs) and tight_ctrs.device == warm.device:
+            if _step_qualifies(tight_ctrs) and tight_ctrs.device == warm.device:
                 tight_ctrs = prepare_sparse(tight_ctrs)
             else:
                 warm = None
@@ -252,7 +252,7 @@ class abstractConeAlignedCosine(optModule):
         if mode not in _WARM_MODES or isinstance(tight_ctrs, PackedBatch):
             return None
         if isinstance(tight_ctrs, SparseCones):
-            if not _step_qualifies_sparse(tight_ctrs):
+            if not _step_qualifies(tight_ctrs):
                 return None
         elif not isinstance(tight_ctrs, PreparedCones) and not (isinstance(tight_ctrs, torch.Tensor) and
                                                                 _warm_dense_ok(tight_ctrs, _op_kwargs(kwargs))):

@@ -22,7 +22,8 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .qpsolver import _grow_limits, _large_guess, _raise_for_status, fast_path_cannot_fit
+from .qpsolver import (_alloc_out, _grow_limits, _large_guess, _launch_packed, _launch_step, _LiteSlots, _out_ptrs, _raise_for_status,
+                       _shape, fast_path_cannot_fit)
 from .sparse import collate_sparse
 
 __all__ = ["ConeStore", "PackedBatch", "collate_ids", "collate_sparse", "prefetch"]
@@ -94,19 +95,10 @@ class ConeStore:
         (TSP-100: 102 MB per instance)."""
         lib = _lib.load()
         dev = torch.device("cuda", torch.cuda.current_device())
-
-        class _Chunks:
-            def __iter__(self):
-                return (make_chunk(k) for k in keys)
-
-        chunks = _Chunks()
-        d = None  # known once the first chunk has been produced
         stream = _lib.current_stream()
-        # pass 1: counts.  Default launch limits are sized for small structured cones; a chunk that does
-        # not fit is re-counted with one wave per instance and the full 160 KiB arena, then on the
-        # large-cone path (global workspace).  lim = (nnz_cap, lds_bytes, waves) or ("large", nnz_cap).
+
         def pack_large(x, cap, n_rows, n_nnz, store, slot, status):
-            B, m, _ = x.shape
+            B, m, d = x.shape
             slice_bytes = int(lib.cave_hip_large_slice_bytes(m, d, cap, 1))
             slots = _lib.large_slots(dev, B, slice_bytes)
             ws = _lib.workspace(dev, slots * slice_bytes)
@@ -114,58 +106,86 @@ class ConeStore:
                                                _lib.ptr(n_rows), _lib.ptr(n_nnz), store, slot, _lib.ptr(status), stream),
                        "cave_hip_pack_large")
 
-        counts, limits = [], []
-        for ch in chunks:
-            x = ch.to(device=dev, dtype=torch.float32).contiguous()
-            del ch
-            B, m, _ = x.shape
-            if d is None:
-                d = int(x.shape[2])
+        def count(x, lim, n_rows, n_nnz, status):
+            _lib.check(lib.cave_hip_pack_count(_lib.ptr(x), *x.shape, *lim, _lib.ptr(n_rows), _lib.ptr(n_nnz),
+                                               _lib.ptr(status), stream), "cave_hip_pack_count")
+
+        def fill(x, lim, store, slot, status):
+            _lib.check(lib.cave_hip_pack_fill(_lib.ptr(x), *x.shape, *lim, store, slot, _lib.ptr(status), stream),
+                       "cave_hip_pack_fill")
+
+        def large_caps(x):  # the host does not know the non-zero counts: a guess, then x4 up to the dense block
+            _, m, d = x.shape
+            cap = _large_guess(m, d)[0]
+            for attempt in range(5):
+                yield cap
+                cap = min(4 * cap, max(m * d, 64))
+
+        return cls._build(dev, keys, lambda k: make_chunk(k).to(device=dev, dtype=torch.float32).contiguous(), count, fill,
+                          pack_large, large_caps, lambda status, what, lo: _raise_for_status(status, what))
+
+    @classmethod
+    def _build(cls, dev, keys, load, count, fill, pack_large, large_caps, raise_for, tolerate_bad: bool = False) -> "ConeStore":
+        """The two-pass build of both wire formats.  `load(key)` puts a chunk on the device (called twice per chunk);
+        `count(x, lim, n_rows, n_nnz, status)`, `fill(x, lim, store, slot, status)` and `pack_large(x, cap, n_rows, n_nnz,
+        store, slot, status)` are the format's pack launches; `large_caps(x)` yields the non-zero capacities the large
+        path tries; `raise_for(status, what, lo)` raises for a chunk starting at instance `lo`.  `tolerate_bad`: an
+        instance the device rejected (ST_BAD_INPUT) is left as an empty cone and marked in `bad_input`."""
+        # pass 1: counts.  Default launch limits are sized for small structured cones; a chunk that does
+        # not fit is re-counted with one wave per instance and the full 160 KiB arena, then on the
+        # large-cone path (global workspace).  lim = (nnz_cap, lds_bytes, waves) or ("large", nnz_cap).
+        counts, limits, bad_chunks = [], [], []
+        lo, d = 0, None  # d: known once the first chunk has been produced
+        for key in keys:
+            x = load(key)
+            B, m, d = _shape(x)
             n_rows = torch.empty(B, dtype=torch.int32, device=dev)
             n_nnz = torch.empty(B, dtype=torch.int32, device=dev)
             status = torch.empty(B, dtype=torch.int32, device=dev)
             lim = (0, 0, 0)
             tier = 2 if fast_path_cannot_fit(d) else 0
-            while True:
-                if tier < 2:
-                    _lib.check(lib.cave_hip_pack_count(_lib.ptr(x), B, m, d, lim[0], lim[1], lim[2], _lib.ptr(n_rows),
-                                                       _lib.ptr(n_nnz), _lib.ptr(status), stream), "cave_hip_pack_count")
-                    if bool((status == _lib.ST_TOO_LARGE).any()):
-                        tier += 1
-                        if tier == 1:
-                            cap, lds = _grow_limits(m, d)
-                            lim = (cap, lds, 8)
-                        continue
+            while tier < 2:
+                count(x, lim, n_rows, n_nnz, status)
+                if not bool((status == _lib.ST_TOO_LARGE).any()):
                     break
-                cap = _large_guess(m, d)[0]
-                for attempt in range(5):
+                tier += 1
+                if tier == 1:
+                    cap, lds = _grow_limits(m, d)
+                    lim = (cap, lds, 8)
+            if tier == 2:
+                for cap in large_caps(x):
                     pack_large(x, cap, n_rows, n_nnz, None, 0, status)
                     if not bool((status == _lib.ST_TOO_LARGE).any()):
                         break
-                    cap = min(4 * cap, max(m * d, 64))
                 lim = ("large", cap)
-                break
-            _raise_for_status(status, "ConeStore pack")
+            if tolerate_bad:
+                bad_chunks.append(status == _lib.ST_BAD_INPUT)
+                status = torch.where(bad_chunks[-1], torch.zeros_like(status), status)
+            raise_for(status, "ConeStore pack", lo)
             counts.append((n_rows, n_nnz))
             limits.append(lim)
+            lo += B
         if d is None:
             raise ValueError("ConeStore: no chunks")
         self = cls(d, dev)
         self._allocate(counts)
         # pass 2: fill
-        slot = 0
-        for ch, lim in zip(chunks, limits):
-            x = ch.to(device=dev, dtype=torch.float32).contiguous()
-            B, m, _ = x.shape
+        lo = 0
+        for key, lim in zip(keys, limits):
+            x = load(key)
+            B = _shape(x)[0]
             status = torch.empty(B, dtype=torch.int32, device=dev)
             if lim[0] == "large":
-                pack_large(x, lim[1], None, None, C.byref(self._c), slot, status)
+                pack_large(x, lim[1], None, None, C.byref(self._c), lo, status)
             else:
-                _lib.check(lib.cave_hip_pack_fill(_lib.ptr(x), B, m, d, lim[0], lim[1], lim[2], C.byref(self._c), slot,
-                                                  _lib.ptr(status), stream), "cave_hip_pack_fill")
-            _raise_for_status(status, "ConeStore fill")
-            slot += B
+                fill(x, lim, C.byref(self._c), lo, status)
+            if tolerate_bad:
+                status = torch.where(status == _lib.ST_BAD_INPUT, torch.zeros_like(status), status)
+            raise_for(status, "ConeStore fill", lo)
+            lo += B
         self._finish_build()
+        bad = torch.cat(bad_chunks) if bad_chunks else None
+        self.bad_input = bad if bad is not None and bool(bad.any()) else None
         return self
 
     def _allocate(self, counts) -> None:
@@ -177,25 +197,10 @@ class ConeStore:
         z = torch.zeros(1, dtype=torch.int64, device=dev)
         row_off = torch.cat([z, torch.cumsum(n_rows, 0)])
         nnz_off = torch.cat([z, torch.cumsum(n_nnz, 0)])
-        R, Z = int(row_off[-1]), int(nnz_off[-1])
         self.n = N
         self.max_rows = int(n_rows.max()) if N else 0
         self.max_nnz = int(n_nnz.max()) if N else 0
-        t = self.t
-        t["row_off"], t["nnz_off"] = row_off, nnz_off
-        t["n_valid"] = torch.zeros(N, dtype=torch.int32, device=dev)
-        t["flags"] = torch.zeros(N, dtype=torch.uint8, device=dev)
-        t["usign"] = torch.zeros(N * d, dtype=torch.uint8, device=dev)
-        t["avg"] = torch.zeros(N * d, dtype=torch.float32, device=dev)
-        t["vkind"] = torch.zeros(max(R, 1), dtype=torch.uint8, device=dev)
-        t["rlo"] = torch.zeros(max(R, 1), dtype=torch.int32, device=dev)
-        t["rhi"] = torch.zeros(max(R, 1), dtype=torch.int32, device=dev)
-        t["ccol"] = torch.zeros(max(Z, 1), dtype=torch.int16, device=dev)
-        t["cval"] = torch.zeros(max(Z, 1), dtype=torch.float32, device=dev)
-        t["cptr"] = torch.zeros(N * (d + 1), dtype=torch.int32, device=dev)
-        t["cvar"] = torch.zeros(max(Z, 1), dtype=torch.int16, device=dev)
-        t["cvalc"] = torch.zeros(max(Z, 1), dtype=torch.float32, device=dev)
-        self._c = _lib.Store(n=N, d=d, reserved=0, **{k: v.data_ptr() for k, v in t.items()})
+        self.t, self._c = _lib.alloc_store(dev, d, row_off, nnz_off, int(row_off[-1]), int(nnz_off[-1]))
 
     def _finish_build(self) -> None:
         """What follows the fill pass, whichever wire format it read: launch figures of the store, sign folding,
@@ -255,16 +260,13 @@ class ConeStore:
         ``strict=False`` it is left as an empty cone and marked in `store.bad_input` ([n] bool, else None)."""
         lib = _lib.load()
         dev = cones.device if cones.is_cuda else torch.device("cuda", torch.cuda.current_device())
-        d, m = cones.d, cones.m_max
-        if len(cones) == 0:
-            raise ValueError("ConeStore: no chunks")
         chunk = max(1, int(chunk))
         spans = [(i, min(i + chunk, len(cones))) for i in range(0, len(cones), chunk)]
         with torch.cuda.device(dev):
             stream = _lib.current_stream()
 
             def pack_large(x, cap, n_rows, n_nnz, store, slot, status):
-                slice_bytes = int(lib.cave_hip_large_slice_bytes(m, d, cap, 1))
+                slice_bytes = int(lib.cave_hip_large_slice_bytes(x.m_max, x.d, cap, 1))
                 # one workgroup per compute unit: the workspace (1.8 MB per slot at TSP-100) is then the largest transient
                 # of the build, and stays below what the dense route stages for four instances
                 slots = min(_lib.large_slots(dev, len(x), slice_bytes), 256)
@@ -273,52 +275,18 @@ class ConeStore:
                                                           _lib.ptr(n_nnz), store, slot, _lib.ptr(status), stream),
                            "cave_hip_pack_large_sparse")
 
-            counts, limits, bad_chunks = [], [], []
-            for lo, hi in spans:
-                x = cones[lo:hi].to(dev)
-                B = hi - lo
-                n_rows = torch.empty(B, dtype=torch.int32, device=dev)
-                n_nnz = torch.empty(B, dtype=torch.int32, device=dev)
-                status = torch.empty(B, dtype=torch.int32, device=dev)
-                lim = (0, 0, 0)
-                tier = 2 if fast_path_cannot_fit(d) else 0
-                while tier < 2:
-                    _lib.check(lib.cave_hip_pack_count_sparse(x.c_ref(), lim[0], lim[1], lim[2], _lib.ptr(n_rows),
-                                                              _lib.ptr(n_nnz), _lib.ptr(status), stream),
-                               "cave_hip_pack_count_sparse")
-                    if not bool((status == _lib.ST_TOO_LARGE).any()):
-                        break
-                    tier += 1
-                    if tier == 1:
-                        cap, lds = _grow_limits(m, d)
-                        lim = (cap, lds, 8)
-                if tier == 2:
-                    cap = max(64, int(x.nnz_per_instance.max()))
-                    pack_large(x, cap, n_rows, n_nnz, None, 0, status)
-                    lim = ("large", cap)
-                if not strict:
-                    bad_chunks.append(status == _lib.ST_BAD_INPUT)
-                    status = torch.where(bad_chunks[-1], torch.zeros_like(status), status)
-                _raise_for_status(status, "ConeStore pack", sparse=True, offset=lo)
-                counts.append((n_rows, n_nnz))
-                limits.append(lim)
-            self = cls(d, dev)
-            self._allocate(counts)
-            for (lo, hi), lim in zip(spans, limits):
-                x = cones[lo:hi].to(dev)
-                status = torch.empty(hi - lo, dtype=torch.int32, device=dev)
-                if lim[0] == "large":
-                    pack_large(x, lim[1], None, None, C.byref(self._c), lo, status)
-                else:
-                    _lib.check(lib.cave_hip_pack_fill_sparse(x.c_ref(), lim[0], lim[1], lim[2], C.byref(self._c), lo,
-                                                             _lib.ptr(status), stream), "cave_hip_pack_fill_sparse")
-                if not strict:
-                    status = torch.where(status == _lib.ST_BAD_INPUT, torch.zeros_like(status), status)
-                _raise_for_status(status, "ConeStore fill", sparse=True, offset=lo)
-            self._finish_build()
-            bad = torch.cat(bad_chunks) if bad_chunks else None
-            self.bad_input = bad if bad is not None and bool(bad.any()) else None
-        return self
+            def count(x, lim, n_rows, n_nnz, status):
+                _lib.check(lib.cave_hip_pack_count_sparse(x.c_ref(), *lim, _lib.ptr(n_rows), _lib.ptr(n_nnz), _lib.ptr(status),
+                                                          stream), "cave_hip_pack_count_sparse")
+
+            def fill(x, lim, store, slot, status):
+                _lib.check(lib.cave_hip_pack_fill_sparse(x.c_ref(), *lim, store, slot, _lib.ptr(status), stream),
+                           "cave_hip_pack_fill_sparse")
+
+            return cls._build(dev, spans, lambda span: cones[span[0]:span[1]].to(dev), count, fill, pack_large,
+                              lambda x: (max(64, int(x.nnz_per_instance.max())),),  # the host knows the counts: one attempt
+                              lambda status, what, lo: _raise_for_status(status, what, sparse=True, offset=lo),
+                              tolerate_bad=not strict)
 
     @classmethod
     def from_sparse_shard(cls, cones, rank: int, world: int, chunk: int = 1024) -> "ConeStore":
@@ -338,8 +306,6 @@ class ConeStore:
         build its index structures ONCE -- a lite store beside the packed one (cave_hip_lite_from_packed) -- and serve
         batches of up to 2048 ids through the solve half of the step kernel (cave_hip_cone_step: 7 KB per instance in
         one memory round trip, no per-call build of the structures, the lite-only code object)."""
-        from .qpsolver import _LiteSlots
-
         self.lite_slots = None
         if not self.lite or self.large or self.n == 0:
             return
@@ -462,17 +428,12 @@ class ConeStore:
             pred = pred_cost.detach()
             if pred.device != dev or pred.dtype != torch.float32 or not pred.is_contiguous():
                 pred = pred.to(device=dev, dtype=torch.float32).contiguous()
-        out: dict[str, torch.Tensor] = {}
         other_device = torch.cuda.current_device() != dev.index
         if other_device:
             ctx = torch.cuda.device(dev)
             ctx.__enter__()
         try:
-            for name in outputs:
-                out[name] = torch.empty((B,) if name in ("rnorm", "loss") else (B, d), dtype=torch.float32, device=dev)
-            status = torch.empty(B, dtype=torch.int32, device=dev)
-            iters = torch.empty(B, dtype=torch.int32, device=dev)
-            out["status"], out["iters"] = status, iters
+            out, status, iters = _alloc_out(outputs, B, d, dev)
             if B == 0:
                 return out
             if self.large:
@@ -482,14 +443,10 @@ class ConeStore:
                 rc = lib.cave_hip_cone_packed_large(
                     C.byref(self._c), _lib.ptr(ids), _lib.ptr(pred), B, int(mode), float(sign), float(inner_ratio),
                     int(max_iter), self.large_lds, int(self.large_waves), _lib.ptr(ws), slice_bytes, slots,
-                    _lib.ptr(out.get("proj")), _lib.ptr(out.get("rnorm")), _lib.ptr(out.get("target")),
-                    _lib.ptr(out.get("loss")), _lib.ptr(out.get("grad")), _lib.ptr(status), _lib.ptr(iters),
-                    _lib.current_stream())
+                    *_out_ptrs(out, status, iters), _lib.current_stream())
                 _lib.check(rc, "cave_hip_cone_packed_large")
             elif (self.lite_slots is not None and B <= 2048 and self.waves == 0
                   and (mode == _lib.MODE_INNER_IPM or not self.warm_start or getattr(self, "lite_warm", None) is not None)):
-                from .qpsolver import _launch_step
-
                 # (warm start: the multiplier cache keyed by store slot; out["warm_hit"] marks the instances that hit.
                 #  The interior-point mode has a kernel of its own and always runs cold: no cache, no "warm_hit")
                 warm = self.lite_warm if self.warm_start and mode != _lib.MODE_INNER_IPM else None
@@ -501,13 +458,8 @@ class ConeStore:
                 lds = self.lds_bytes if B <= 2048 else self.lds_bytes_big
                 if self.lds_bytes_diet and B > self.diet_min_batch and mode != _lib.MODE_INNER_IPM and self.waves in (0, 8):
                     lds = self.lds_bytes_diet  # two workgroups per compute unit
-                rc = lib.cave_hip_cone_packed(
-                    C.byref(self._c), _lib.ptr(ids), _lib.ptr(pred), B, int(mode), float(sign), float(inner_ratio),
-                    int(max_iter), lds, self._waves_for(B),
-                    _lib.ptr(out.get("proj")), _lib.ptr(out.get("rnorm")), _lib.ptr(out.get("target")),
-                    _lib.ptr(out.get("loss")), _lib.ptr(out.get("grad")), _lib.ptr(status), _lib.ptr(iters),
-                    _lib.current_stream())
-                _lib.check(rc, "cave_hip_cone_packed")
+                _launch_packed(C.byref(self._c), ids, pred, B, mode, sign, inner_ratio, max_iter, lds, self._waves_for(B),
+                               out, status, iters)
             self.last_iters = iters  # Newton iterations / status of the most recent call (device tensors; diagnostics)
             self.last_status = status
             if check:

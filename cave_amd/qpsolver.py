@@ -16,11 +16,14 @@ status codes into the reference's error behaviour.
 
 from __future__ import annotations
 
+import ctypes as C
+
 import torch
 
 from . import _lib
 from ._lib import (MODE_AVG, MODE_EXACT, MODE_HEURISTIC, MODE_INNER, MODE_PROJECT, ST_BAD_INPUT,
                    ST_NOT_CONVERGED, ST_OK, ST_TOO_LARGE)
+from .sparse import SparseCones
 
 __all__ = ["project_hip", "average_ctrs_hip", "cone_op_dense", "HipSolverError", "PreparedCones", "prepare_dense",
            "prepare_sparse", "prepare_cones", "cone_op_prepared", "step_lds_bytes", "cone_op_sparse", "project_hip_sparse"]
@@ -115,29 +118,9 @@ _sparse_split_ok: dict[tuple[int, int], bool] = {}  # the same for batches on th
 
 class _SlotStore:
     def __init__(self, dev, B: int, d: int):
-        import ctypes as C
-
         self.B, self.d = B, d
-        t = {}
         ar = torch.arange(B + 1, dtype=torch.int64, device=dev)
-        t["row_off"], t["nnz_off"] = ar * SPLIT_ROWS, ar * SPLIT_NNZ
-        R, Z = B * SPLIT_ROWS, B * SPLIT_NNZ
-        t["n_valid"] = torch.zeros(B, dtype=torch.int32, device=dev)
-        t["flags"] = torch.zeros(B, dtype=torch.uint8, device=dev)
-        t["usign"] = torch.zeros(B * d, dtype=torch.uint8, device=dev)
-        t["avg"] = torch.zeros(B * d, dtype=torch.float32, device=dev)
-        t["vkind"] = torch.zeros(R, dtype=torch.uint8, device=dev)
-        t["rlo"] = torch.zeros(R, dtype=torch.int32, device=dev)
-        t["rhi"] = torch.zeros(R, dtype=torch.int32, device=dev)
-        t["ccol"] = torch.zeros(Z, dtype=torch.int16, device=dev)
-        t["cval"] = torch.zeros(Z, dtype=torch.float32, device=dev)
-        t["cptr"] = torch.zeros(B * (d + 1), dtype=torch.int32, device=dev)
-        t["cvar"] = torch.zeros(Z, dtype=torch.int16, device=dev)
-        t["cvalc"] = torch.zeros(Z, dtype=torch.float32, device=dev)
-        t["n_rows"] = torch.zeros(B, dtype=torch.int32, device=dev)
-        t["n_nnz"] = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.t = t
-        self.c = _lib.Store(n=B, d=d, reserved=0, **{k: v.data_ptr() for k, v in t.items()})
+        self.t, self.c = _lib.alloc_store(dev, d, ar * SPLIT_ROWS, ar * SPLIT_NNZ, B * SPLIT_ROWS, B * SPLIT_NNZ, slot_mode=True)
         self.ref = C.byref(self.c)
         self.pack_status = torch.empty(B, dtype=torch.int32, device=dev)
         self.lds_bytes = int(_lib.load_library().cave_hip_packed_lds_bytes(d, SPLIT_ROWS, SPLIT_NNZ, 1))
@@ -151,6 +134,8 @@ def _slot_store(dev, B: int, d: int) -> _SlotStore:
         if len(_slot_stores) >= 4:
             _slot_stores.pop(next(iter(_slot_stores)))
         st = _slot_stores[key] = _SlotStore(dev, B, d)
+    if st.lds_bytes <= 0:
+        raise HipSolverError("split form: no LDS configuration")
     return st
 
 
@@ -177,8 +162,6 @@ class _LiteSlots:
     device-resident ConeStore, of all its instances)."""
 
     def __init__(self, dev, B: int, d: int):
-        import ctypes as C
-
         self.B, self.d = B, d
         t = {
             "hdr": torch.zeros(B * 8, dtype=torch.int32, device=dev),
@@ -243,7 +226,7 @@ class PreparedCones:
     def __init__(self, ctrs, store: _LiteSlots, gen: int):
         self.ctrs, self.store, self.gen = ctrs, store, gen
         self.sparse = not isinstance(ctrs, torch.Tensor)
-        self.shape = (len(ctrs), ctrs.m_max, ctrs.d) if self.sparse else tuple(ctrs.shape)
+        self.shape = _shape(ctrs)
         self.follow = None   # the batch after this one (consumed by the first solve)
         self.next = None     # what to pass for that batch: a PreparedCones, or the batch itself
 
@@ -266,118 +249,107 @@ class PreparedCones:
         return self.ctrs.device
 
 
-def _step_qualifies(t) -> bool:
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 3):
+def _shape(x) -> tuple[int, int, int]:
+    """(B, m_max, d) of a batch of cones on either wire format."""
+    return tuple(x.shape) if isinstance(x, torch.Tensor) else (len(x), x.m_max, x.d)
+
+
+def _step_qualifies(x) -> bool:
+    """The fused step takes this batch: a dense (B, m_max, d) tensor or a SparseCones, on the device.  The rules on
+    (B, m_max, d) and the verdicts are the same for both (`_step_ok` is shared: from the same non-zeros the two pack halves
+    refuse the same cones); the sparse pack half keeps row indices in 15 bits."""
+    if isinstance(x, torch.Tensor):
+        if not (x.is_cuda and x.dim() == 3):
+            return False
+    elif not (isinstance(x, SparseCones) and x.is_cuda and x.m_max <= 32767):
         return False
-    B, m, d = t.shape
+    B, m, d = _shape(x)
     return 0 < m and d <= SPLIT_MAX_D and 0 < B <= STEP_MAX_B and _step_ok.get((m, d)) is not False and step_lds_bytes(m, d) > 0
 
 
-def _step_qualifies_sparse(x) -> bool:
-    """_step_qualifies for a SparseCones: the same rules on (B, m_max, d) and the same verdicts (`_step_ok` is shared
-    with the dense route: from the same non-zeros the two pack halves refuse the same cones)."""
-    from .sparse import SparseCones
-
-    if not (isinstance(x, SparseCones) and x.is_cuda):
-        return False
-    B, m, d = len(x), x.m_max, x.d
-    return 0 < m <= 32767 and d <= SPLIT_MAX_D and 0 < B <= STEP_MAX_B and _step_ok.get((m, d)) is not False and step_lds_bytes(m, d) > 0
+_step_qualifies_sparse = _step_qualifies
 
 
-def _launch_step_sparse(solve, pred, B, mode, sign, inner_ratio, max_iter, out, status, iters, nxt_cones, nxt_store,
-                        zero_failed=False, warm=None, keys=None):
-    """_launch_step with the next batch on the sparse wire format (cave_hip_cone_step_sparse; mode INNER_IPM:
-    cave_hip_cone_step_sparse_ipm, which has no cache -- `warm` is ignored, the mode runs cold)."""
-    lib = _lib.load()
-    dev = nxt_cones.device
-    if mode == _lib.MODE_INNER_IPM and B > 0:
-        rc = lib.cave_hip_cone_step_sparse_ipm(
-            solve.ref if solve is not None else None, None, _lib.ptr(pred), B, float(sign), int(max_iter), 1 if zero_failed else 0,
-            _lib.ptr(out.get("proj")), _lib.ptr(out.get("rnorm")), _lib.ptr(out.get("target")), _lib.ptr(out.get("loss")),
-            _lib.ptr(out.get("grad")), _lib.ptr(status), _lib.ptr(iters),
-            nxt_cones.c_ref(), nxt_store.ref, _lib.ptr(nxt_store.pack_status), _lib.ptr(_tickets_for(dev)), _lib.current_stream())
-        _lib.check(rc, "cave_hip_cone_step_sparse_ipm")
-        return
-    hit = None
-    if warm is not None and B > 0:
-        hit = out["warm_hit"] = torch.empty(B, dtype=torch.uint8, device=dev)
-    rc = lib.cave_hip_cone_step_sparse(
-        solve.ref if solve is not None else None, None, _lib.ptr(pred), B, int(mode), float(sign), float(inner_ratio),
-        int(max_iter), 1 if zero_failed else 0,
-        _lib.ptr(out.get("proj")), _lib.ptr(out.get("rnorm")), _lib.ptr(out.get("target")), _lib.ptr(out.get("loss")),
-        _lib.ptr(out.get("grad")), _lib.ptr(status), _lib.ptr(iters),
-        nxt_cones.c_ref(), nxt_store.ref, _lib.ptr(nxt_store.pack_status),
-        warm.ref if hit is not None else None, _lib.ptr(keys), _lib.ptr(hit), _lib.ptr(_tickets_for(dev)), _lib.current_stream())
-    _lib.check(rc, "cave_hip_cone_step_sparse")
+def _alloc_out(outputs, B: int, d: int, dev):
+    """-> (out, status, iters): the outputs asked for ([B] for rnorm / loss, else [B, d]) plus out["status"] / out["iters"]."""
+    out = {name: torch.empty((B,) if name in ("rnorm", "loss") else (B, d), dtype=torch.float32, device=dev) for name in outputs}
+    status = out["status"] = torch.empty(B, dtype=torch.int32, device=dev)
+    iters = out["iters"] = torch.empty(B, dtype=torch.int32, device=dev)
+    return out, status, iters
 
 
-def _launch_step(solve, pred, B, mode, sign, inner_ratio, max_iter, out, status, iters, nxt_ctrs, nxt_store, ids=None,
+def _out_ptrs(out, status, iters) -> tuple:
+    """The seven trailing output pointers of every operator entry point (NULL: not asked for)."""
+    ptr, get = _lib.ptr, out.get
+    return (ptr(get("proj")), ptr(get("rnorm")), ptr(get("target")), ptr(get("loss")), ptr(get("grad")), ptr(status), ptr(iters))
+
+
+def _launch_step(solve, pred, B, mode, sign, inner_ratio, max_iter, out, status, iters, nxt, nxt_store, ids=None,
                  zero_failed=False, warm=None, keys=None):
-    """One launch of the step kernel.  `warm` (a cave_amd.warm.WarmCache): the warm variant, which starts each solve from
-    the cache's multipliers for its key -- `keys` [B] int64, or None: the content of the cone -- and writes the
-    final ones back; out["warm_hit"] [B] uint8 then tells which instances hit.  Mode INNER_IPM goes to the kernel of
-    its own (cave_hip_cone_step_ipm), which has no cache: `warm` is ignored, the mode runs cold."""
+    """One launch of the step kernel: the solve half for `solve` (None / B = 0: pack only) and the pack half for `nxt`
+    into `nxt_store` -- None (solve only), a dense tensor (cave_hip_cone_step) or a SparseCones (cave_hip_cone_step_sparse).
+    `warm` (a cave_amd.warm.WarmCache): the warm variant, which starts each solve from the cache's multipliers for its
+    key -- `keys` [B] int64, or None: the content of the cone -- and writes the final ones back; out["warm_hit"] [B] uint8
+    then tells which instances hit.  Mode INNER_IPM goes to the kernels of its own (cave_hip_cone_step_ipm /
+    _sparse_ipm), which have no cache: `warm` is ignored, the mode runs cold."""
     lib = _lib.load()
-    Bn, mn, dn = (nxt_ctrs.shape if nxt_ctrs is not None else (0, 0, solve.d))
-    dev = status.device if status is not None else nxt_ctrs.device
+    ptr = _lib.ptr
+    sparse = nxt is not None and not isinstance(nxt, torch.Tensor)
+    dev = status.device if status is not None else nxt.device
+    name, cache = "cave_hip_cone_step_sparse" if sparse else "cave_hip_cone_step", ()
+    flag = 1 if zero_failed else 0
     if mode == _lib.MODE_INNER_IPM and B > 0:
-        rc = lib.cave_hip_cone_step_ipm(
-            solve.ref if solve is not None else None, _lib.ptr(ids), _lib.ptr(pred), B, float(sign), int(max_iter),
-            1 if zero_failed else 0,
-            _lib.ptr(out.get("proj")), _lib.ptr(out.get("rnorm")), _lib.ptr(out.get("target")), _lib.ptr(out.get("loss")),
-            _lib.ptr(out.get("grad")), _lib.ptr(status), _lib.ptr(iters),
-            _lib.ptr(nxt_ctrs), Bn, mn, dn, nxt_store.ref if nxt_store is not None else None,
-            _lib.ptr(nxt_store.pack_status) if nxt_store is not None else None, _lib.ptr(_tickets_for(dev)), _lib.current_stream())
-        _lib.check(rc, "cave_hip_cone_step_ipm")
-        return
-    args = (solve.ref if solve is not None else None, _lib.ptr(ids), _lib.ptr(pred), B, int(mode), float(sign), float(inner_ratio),
-            int(max_iter), 1 if zero_failed else 0,
-            _lib.ptr(out.get("proj")), _lib.ptr(out.get("rnorm")), _lib.ptr(out.get("target")), _lib.ptr(out.get("loss")),
-            _lib.ptr(out.get("grad")), _lib.ptr(status), _lib.ptr(iters),
-            _lib.ptr(nxt_ctrs), Bn, mn, dn, nxt_store.ref if nxt_store is not None else None,
-            _lib.ptr(nxt_store.pack_status) if nxt_store is not None else None)
-    if warm is None:
-        rc = lib.cave_hip_cone_step(*args, _lib.ptr(_tickets_for(dev)), _lib.current_stream())
-        _lib.check(rc, "cave_hip_cone_step")
-        return
-    hit = out["warm_hit"] = torch.empty(B, dtype=torch.uint8, device=dev)
-    rc = lib.cave_hip_cone_step_warm(*args, warm.ref, _lib.ptr(keys), _lib.ptr(hit), _lib.ptr(_tickets_for(dev)),
-                                     _lib.current_stream())
-    _lib.check(rc, "cave_hip_cone_step_warm")
+        name += "_ipm"
+        scalars = (float(sign), int(max_iter), flag)
+    else:
+        scalars = (int(mode), float(sign), float(inner_ratio), int(max_iter), flag)
+        if sparse:  # one entry point, cold when its cache is NULL (a pack-only launch has nothing to warm-start)
+            hit = None
+            if warm is not None and B > 0:
+                hit = out["warm_hit"] = torch.empty(B, dtype=torch.uint8, device=dev)
+            cache = (warm.ref if hit is not None else None, ptr(keys), ptr(hit))
+        elif warm is not None:
+            name += "_warm"
+            hit = out["warm_hit"] = torch.empty(B, dtype=torch.uint8, device=dev)
+            cache = (warm.ref, ptr(keys), ptr(hit))
+    if sparse:
+        pack = (nxt.c_ref(), nxt_store.ref, ptr(nxt_store.pack_status))
+    elif nxt is not None:
+        pack = (ptr(nxt), *nxt.shape, nxt_store.ref, ptr(nxt_store.pack_status))
+    else:
+        pack = (None, 0, 0, solve.d, None, None)
+    rc = getattr(lib, name)(solve.ref if solve is not None else None, ptr(ids), ptr(pred), B, *scalars,
+                            *_out_ptrs(out, status, iters), *pack, *cache, ptr(_tickets_for(dev)), _lib.current_stream())
+    _lib.check(rc, name)
 
 
-def prepare_dense(tight_ctrs: torch.Tensor) -> "PreparedCones | torch.Tensor":
-    """Run the pack stage of a dense batch now, on the current stream (a pack-only launch of the step kernel).
-    Returns the tensor itself when the shape does not qualify (the loss call then takes the ordinary path)."""
-    _lib.load()
-    if not _step_qualifies(tight_ctrs):
-        return tight_ctrs
-    dev = tight_ctrs.device
-    ctrs = _as_device(tight_ctrs, dev)
-    B, m, d = ctrs.shape
-    with torch.cuda.device(dev):
-        ss = _take_store(dev, B, d)
-        _launch_step(None, None, 0, MODE_PROJECT, 1.0, 0.0, 0, {}, None, None, ctrs, ss)
-    return PreparedCones(ctrs, ss, ss.gen)
+_launch_step_sparse = _launch_step
 
 
-def prepare_sparse(cones) -> "PreparedCones":
-    """prepare_dense for a batch on the sparse wire format: a pack-only launch of cave_hip_cone_step_sparse into a pooled
-    lite store.  Returns the batch itself (on the device) when the shape does not qualify."""
-    _lib.load()
-    x = cones if cones.is_cuda else cones.cuda()
-    if not _step_qualifies_sparse(x):
-        return x
-    dev = x.device
-    with torch.cuda.device(dev):
-        ss = _take_store(dev, len(x), x.d)
-        _launch_step_sparse(None, None, 0, MODE_PROJECT, 1.0, 0.0, 0, {}, None, None, x, ss)
-    return PreparedCones(x, ss, ss.gen)
+def _on_device(x, dev):
+    """A batch of cones as the kernels read it (float32, contiguous) on `dev`."""
+    return _as_device(x, dev) if isinstance(x, torch.Tensor) else x.to(dev)
 
 
 def prepare_cones(x):
-    """prepare_dense for a tensor, prepare_sparse for a SparseCones."""
-    return prepare_dense(x) if isinstance(x, torch.Tensor) else prepare_sparse(x)
+    """Run the pack stage of a batch -- a dense tensor or a SparseCones -- now, on the current stream: a pack-only launch
+    of the step kernel into a pooled lite store.  Returns the batch itself (a SparseCones: on the device) when the shape
+    does not qualify; the loss call then takes the ordinary path."""
+    _lib.load()
+    if not isinstance(x, torch.Tensor) and not x.is_cuda:
+        x = x.cuda()
+    if not _step_qualifies(x):
+        return x
+    dev = x.device
+    x = _on_device(x, dev)
+    B, _, d = _shape(x)
+    with torch.cuda.device(dev):
+        ss = _take_store(dev, B, d)
+        _launch_step(None, None, 0, MODE_PROJECT, 1.0, 0.0, 0, {}, None, None, x, ss)
+    return PreparedCones(x, ss, ss.gen)
+
+
+prepare_dense = prepare_sparse = prepare_cones
 
 
 def cone_op_prepared(prep: PreparedCones, pred_cost: torch.Tensor, mode: int, sign: float = 1.0, inner_ratio: float = 0.2, *,
@@ -408,33 +380,24 @@ def cone_op_prepared(prep: PreparedCones, pred_cost: torch.Tensor, mode: int, si
     pred = _as_device(pred_cost, dev)
     if pred.shape != (B, d):
         raise ValueError(f"pred_cost must have shape ({B}, {d}), got {tuple(pred.shape)}")
-    out: dict[str, torch.Tensor] = {}
     with torch.cuda.device(dev):
-        for name in outputs:
-            out[name] = torch.empty((B,) if name in ("rnorm", "loss") else (B, d), dtype=torch.float32, device=dev)
-        status = torch.empty(B, dtype=torch.int32, device=dev)
-        iters = torch.empty(B, dtype=torch.int32, device=dev)
-        out["status"], out["iters"] = status, iters
-        nctrs = nstore = None
-        nsparse = False
+        out, status, iters = _alloc_out(outputs, B, d, dev)
+        nxt = nstore = None
         if follow is not None:
-            if _step_qualifies(follow):
-                nctrs = _as_device(follow, dev)
-                nstore = _take_store(dev, int(nctrs.shape[0]), int(nctrs.shape[2]), avoid=prep.store)
-                prep.next = PreparedCones(nctrs, nstore, nstore.gen)
-            elif _step_qualifies_sparse(follow) and follow.device == dev:
-                nctrs, nsparse = follow, True
-                nstore = _take_store(dev, len(nctrs), nctrs.d, avoid=prep.store)
-                prep.next = PreparedCones(nctrs, nstore, nstore.gen)
+            # (a dense batch is moved to this device; a sparse one on another device goes the ordinary way)
+            if _step_qualifies(follow) and (isinstance(follow, torch.Tensor) or follow.device == dev):
+                nxt = _on_device(follow, dev)
+                Bn, _, dn = _shape(nxt)
+                nstore = _take_store(dev, Bn, dn, avoid=prep.store)
+                prep.next = PreparedCones(nxt, nstore, nstore.gen)
             else:
                 prep.next = follow
         if keys is not None and (keys.device != dev or keys.dtype != torch.int64 or not keys.is_contiguous()):
             keys = keys.to(device=dev, dtype=torch.int64).contiguous()
         # the pack status of THIS batch (its store may be packed again by a later launch: keep the verdict now, in stream order)
         bad = (prep.store.pack_status == ST_BAD_INPUT) if prep.sparse else None
-        launch = _launch_step_sparse if nsparse else _launch_step
-        launch(prep.store, pred, B, mode, sign, inner_ratio, max_iter, out, status, iters, nctrs, nstore,
-               zero_failed=zero_failed, warm=warm, keys=keys)
+        _launch_step(prep.store, pred, B, mode, sign, inner_ratio, max_iter, out, status, iters, nxt, nstore,
+                     zero_failed=zero_failed, warm=warm, keys=keys)
         if bad is not None:
             # an instance the sparse loader rejected left slot state -1, which the solve reports as TOO_LARGE: its own
             # verdict is the loader's (as cone_op_sparse)
@@ -473,6 +436,29 @@ def _raise_for_status(status: torch.Tensor, what: str, sparse: bool = False, off
     raise HipSolverError(f"{what}: unknown status {code}")
 
 
+def _device_and_pred(cones, pred_cost, B: int, d: int, mode: int):
+    """What a general operator call starts with: the device it runs on (the cones', else the prediction's, else the
+    current one) and the validated prediction there (None: MODE_AVG only)."""
+    dev = cones.device if cones.is_cuda else (
+        pred_cost.device if pred_cost is not None and pred_cost.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    if pred_cost is not None:
+        if pred_cost.shape != (B, d):
+            raise ValueError(f"pred_cost must have shape ({B}, {d}), got {tuple(pred_cost.shape)}")
+        return dev, _as_device(pred_cost, dev)
+    if mode != MODE_AVG:
+        raise ValueError("pred_cost is required")
+    return dev, None
+
+
+def _launch_packed(store_ref, ids, pred, B, mode, sign, inner_ratio, max_iter, lds, waves, out, status, iters,
+                   what="cave_hip_cone_packed"):
+    """cave_hip_cone_packed on a store: slots `ids`, or slots [0, B) of a slot store (ids None)."""
+    rc = _lib.load_library().cave_hip_cone_packed(
+        store_ref, _lib.ptr(ids), _lib.ptr(pred), B, int(mode), float(sign), float(inner_ratio), int(max_iter), lds, waves,
+        *_out_ptrs(out, status, iters), _lib.current_stream())
+    _lib.check(rc, what)
+
+
 def cone_op_dense(tight_ctrs: torch.Tensor, pred_cost: torch.Tensor | None, mode: int, sign: float = 1.0,
                   inner_ratio: float = 0.2, *, max_iter: int = 0, nnz_cap: int = 0, lds_bytes: int = 0,
                   waves: int = 0, check: bool = True, outputs: tuple[str, ...] = ("proj", "rnorm")) -> dict[str, torch.Tensor]:
@@ -491,24 +477,10 @@ def cone_op_dense(tight_ctrs: torch.Tensor, pred_cost: torch.Tensor | None, mode
     if tight_ctrs.dim() != 3:
         raise ValueError("tight_ctrs must have shape (B, m_max, d)")
     B, m, d = tight_ctrs.shape
-    dev = tight_ctrs.device if tight_ctrs.is_cuda else (
-        pred_cost.device if pred_cost is not None and pred_cost.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    dev, pred = _device_and_pred(tight_ctrs, pred_cost, B, d, mode)
     ctrs = _as_device(tight_ctrs, dev)
-    pred = None
-    if pred_cost is not None:
-        if pred_cost.shape != (B, d):
-            raise ValueError(f"pred_cost must have shape ({B}, {d}), got {tuple(pred_cost.shape)}")
-        pred = _as_device(pred_cost, dev)
-    elif mode != MODE_AVG:
-        raise ValueError("pred_cost is required")
-    out: dict[str, torch.Tensor] = {}
     with torch.cuda.device(dev):
-        for name in outputs:
-            shape = (B,) if name in ("rnorm", "loss") else (B, d)
-            out[name] = torch.empty(shape, dtype=torch.float32, device=dev)
-        status = torch.empty(B, dtype=torch.int32, device=dev)
-        iters = torch.empty(B, dtype=torch.int32, device=dev)
-        out["status"], out["iters"] = status, iters
+        out, status, iters = _alloc_out(outputs, B, d, dev)
         if B == 0:
             return out
 
@@ -516,9 +488,7 @@ def cone_op_dense(tight_ctrs: torch.Tensor, pred_cost: torch.Tensor | None, mode
             rc = lib.cave_hip_cone_dense(
                 _lib.ptr(ctrs), _lib.ptr(pred), B, m, d, int(mode), float(sign), float(inner_ratio),
                 int(max_iter), int(cap), int(lds), int(nw),
-                _lib.ptr(out.get("proj")), _lib.ptr(out.get("rnorm")), _lib.ptr(out.get("target")),
-                _lib.ptr(out.get("loss")), _lib.ptr(out.get("grad")), _lib.ptr(status), _lib.ptr(iters),
-                _lib.current_stream())
+                *_out_ptrs(out, status, iters), _lib.current_stream())
             _lib.check(rc, "cave_hip_cone_dense")
 
         # LDS of the large path's hot arrays (band window + staging).  The band is only known inside the
@@ -535,9 +505,7 @@ def cone_op_dense(tight_ctrs: torch.Tensor, pred_cost: torch.Tensor | None, mode
             rc = lib.cave_hip_cone_dense_large(
                 _lib.ptr(ctrs), _lib.ptr(pred), B, m, d, int(mode), float(sign), float(inner_ratio),
                 int(max_iter), int(cap), large_lds, _lib.ptr(ws), slice_bytes, slots,
-                _lib.ptr(out.get("proj")), _lib.ptr(out.get("rnorm")), _lib.ptr(out.get("target")),
-                _lib.ptr(out.get("loss")), _lib.ptr(out.get("grad")), _lib.ptr(status), _lib.ptr(iters),
-                _lib.current_stream())
+                *_out_ptrs(out, status, iters), _lib.current_stream())
             _lib.check(rc, "cave_hip_cone_dense_large")
 
         def run_large() -> None:
@@ -554,17 +522,11 @@ def cone_op_dense(tight_ctrs: torch.Tensor, pred_cost: torch.Tensor | None, mode
 
         def launch_split() -> None:
             ss = _slot_store(dev, B, d)
-            if ss.lds_bytes <= 0:
-                raise HipSolverError("split form: no LDS configuration")
             rc = lib.cave_hip_pack_fill(_lib.ptr(ctrs), B, m, d, int(nnz_cap), 0, 4, ss.ref, 0, _lib.ptr(ss.pack_status),
                                         _lib.current_stream())
             _lib.check(rc, "cave_hip_pack_fill (slot mode)")
-            rc = lib.cave_hip_cone_packed(
-                ss.ref, None, _lib.ptr(pred), B, int(mode), float(sign), float(inner_ratio), int(max_iter), ss.lds_bytes, 1,
-                _lib.ptr(out.get("proj")), _lib.ptr(out.get("rnorm")), _lib.ptr(out.get("target")),
-                _lib.ptr(out.get("loss")), _lib.ptr(out.get("grad")), _lib.ptr(status), _lib.ptr(iters),
-                _lib.current_stream())
-            _lib.check(rc, "cave_hip_cone_packed (slot mode)")
+            _launch_packed(ss.ref, None, pred, B, mode, sign, inner_ratio, max_iter, ss.lds_bytes, 1, out, status, iters,
+                           "cave_hip_cone_packed (slot mode)")
 
         # small cones: the split form, once a checked batch of this shape has fitted it (or when this call is checked)
         if auto and waves == 0 and 0 < m and d <= SPLIT_MAX_D and B <= 2048 and (m, d) not in _tier:
@@ -637,50 +599,26 @@ def cone_op_sparse(cones, pred_cost: torch.Tensor | None, mode: int, sign: float
     A malformed instance (unsorted or repeated key, row / column out of range, zero or non-finite value) is rejected
     on the device: ``check=True`` raises ValueError naming the first one; ``check=False`` leaves status
     CAVE_ST_BAD_INPUT and NaN outputs at its index and the other instances correct."""
-    from .sparse import SparseCones
-
     lib = _lib.load()
     if not isinstance(cones, SparseCones):
         raise TypeError("cone_op_sparse: cones must be a SparseCones")
-    B, m, d = len(cones), cones.m_max, cones.d
-    dev = cones.device if cones.is_cuda else (
-        pred_cost.device if pred_cost is not None and pred_cost.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    B, m, d = _shape(cones)
+    dev, pred = _device_and_pred(cones, pred_cost, B, d, mode)
     x = cones.to(dev)
-    pred = None
-    if pred_cost is not None:
-        if pred_cost.shape != (B, d):
-            raise ValueError(f"pred_cost must have shape ({B}, {d}), got {tuple(pred_cost.shape)}")
-        pred = _as_device(pred_cost, dev)
-    elif mode != MODE_AVG:
-        raise ValueError("pred_cost is required")
     what = "solver='hip' (sparse cones)"
     with torch.cuda.device(dev):
         if B == 0:
-            out = {name: torch.empty((0,) if name in ("rnorm", "loss") else (0, d), dtype=torch.float32, device=dev)
-                   for name in outputs}
-            out["status"] = out["iters"] = torch.empty(0, dtype=torch.int32, device=dev)
-            return out
+            return _alloc_out(outputs, 0, d, dev)[0]
         if 0 < m and d <= SPLIT_MAX_D and B <= 2048 and _sparse_split_ok.get((m, d)) is not False:
-            out: dict[str, torch.Tensor] = {}
-            for name in outputs:
-                out[name] = torch.empty((B,) if name in ("rnorm", "loss") else (B, d), dtype=torch.float32, device=dev)
-            status = torch.empty(B, dtype=torch.int32, device=dev)
-            iters = torch.empty(B, dtype=torch.int32, device=dev)
+            out, status, iters = _alloc_out(outputs, B, d, dev)
             ss = _slot_store(dev, B, d)
-            if ss.lds_bytes <= 0:
-                raise HipSolverError("split form: no LDS configuration")
             rc = lib.cave_hip_pack_fill_sparse(x.c_ref(), 0, 0, 4, ss.ref, 0, _lib.ptr(ss.pack_status), _lib.current_stream())
             _lib.check(rc, "cave_hip_pack_fill_sparse (slot mode)")
-            rc = lib.cave_hip_cone_packed(
-                ss.ref, None, _lib.ptr(pred), B, int(mode), float(sign), float(inner_ratio), int(max_iter), ss.lds_bytes, 1,
-                _lib.ptr(out.get("proj")), _lib.ptr(out.get("rnorm")), _lib.ptr(out.get("target")),
-                _lib.ptr(out.get("loss")), _lib.ptr(out.get("grad")), _lib.ptr(status), _lib.ptr(iters),
-                _lib.current_stream())
-            _lib.check(rc, "cave_hip_cone_packed (slot mode)")
+            _launch_packed(ss.ref, None, pred, B, mode, sign, inner_ratio, max_iter, ss.lds_bytes, 1, out, status, iters,
+                           "cave_hip_cone_packed (slot mode)")
             # an instance the loader rejected left an empty slot, which the solve reports as TOO_LARGE (NaN outputs):
             # its own verdict is the loader's
-            status = torch.where(ss.pack_status == ST_BAD_INPUT, ss.pack_status, status)
-            out["status"], out["iters"] = status, iters
+            status = out["status"] = torch.where(ss.pack_status == ST_BAD_INPUT, ss.pack_status, status)
             if not check:
                 return out
             st = status.cpu()
