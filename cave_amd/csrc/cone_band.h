@@ -468,6 +468,10 @@ CAVE_NOINLINE void solve_spd_band(C& c_, const double* Hb_, int bw, const double
 // 1/2 (1 + z / sqrt(1 + z^2)) with z = t / mu.  Takes 1 / mu (0: the binary weight) and a reciprocal square root: the
 // weight is evaluated once per coordinate and iteration (TSP-100: 4950 of them; four per band row in band_gen_rows),
 // and sqrt + two divisions were a quarter of the Hessian phase's instructions.
+// Range: zz * zz overflows from |t / mu| = 1.4e154 on (the result is then 1/2, not 0 / 1), and inv_mu = inf with t = 0
+// gives NaN.  solve_cone_impl keeps mu >= 0.03 max|y| min(1e-15, 0.7^it), so neither happens before iteration 985
+// (NaN: 1990) of a cone that does not converge; a caller that raises max_iter that far must clamp inv_mu first
+// (tests/test_ops_emul.py pins both values).
 CAVE_HD double band_weight(uint8_t u, double rk, double inv_mu) {
   if (u == 0) return 1.0;
   if (u == 3) return 0.0;

@@ -26,6 +26,9 @@
 #include "../../cave_amd/csrc/cone_instance.h"
 #include "../../cave_amd/csrc/cone_step.h"
 #include "../prims/prim_entries.h"
+#ifdef CAVE_SIMT_OPS  // the plain build only: the sanitizer and variant builds keep their compile time
+#include "../prims/op_entries.h"
+#endif
 
 using namespace cave;
 
@@ -138,6 +141,23 @@ int32_t prim_impl(const cave_prims::PrimBatch& a, uint64_t seed) {
   return CAVE_OK;
 }
 
+#ifdef CAVE_SIMT_OPS
+// one operator alone (tests/prims/op_entries.h): an exact-size LDS block per case, poisoned before it runs
+template <int OP, int CX, bool PM1>
+int32_t op_impl(const cave_ops::OpCase* cases, int64_t B, uint64_t seed) {
+  using C = typename cave_ops::OpCtx<CX>::type;
+  for (int64_t b = 0; b < B; ++b) {
+    if (!cave_ops::op_case_valid(OP, PM1, cases[b])) return CAVE_E_INVALID;
+    Lds mem(cave_ops::op_lds_bytes(OP, PM1, cases[b]));
+    mem.poison();
+    simt::run_block(C::NT, (unsigned)b, (unsigned)B, [&]() { cave_ops::op_body<OP, CX, PM1>(mem.p, cases[b]); },
+                    seed ? seed + (uint64_t)b : 0);
+  }
+  return CAVE_OK;
+}
+
+#endif  // CAVE_SIMT_OPS
+
 bool lite_store_ok(const cave_lite_store* s, int64_t need, int64_t d) {  // (as cave_hip.hip)
   return s && s->n >= need && s->d == d && s->hdr && s->usign && s->avg && s->rowptr && s->ell && s->csr16 && s->rl &&
          (((uintptr_t)s->ell | (uintptr_t)s->csr16) & 15u) == 0;
@@ -167,6 +187,28 @@ int64_t cave_simt_prim_info(int32_t kind, int32_t what, int32_t p, int32_t nF, i
   }
   return -1;
 }
+
+#ifdef CAVE_SIMT_OPS
+// ---- the operators alone (tests/prims/op_entries.h)
+int32_t cave_simt_op_run(int32_t kind, const cave_ops::OpCase* cases, int64_t B, uint64_t seed) {
+  using namespace cave_ops;
+  if (!cases || B < 0) return CAVE_E_INVALID;
+  switch (kind) {
+#define CAVE_OP_CASE(OP, CX, PM1) case op_kind(OP, CX, PM1): return op_impl<OP, CX, PM1>(cases, B, seed);
+    CAVE_OP_KINDS(CAVE_OP_CASE)
+#undef CAVE_OP_CASE
+  }
+  return CAVE_E_INVALID;
+}
+int32_t cave_simt_op_case_bytes(void) { return (int32_t)sizeof(cave_ops::OpCase); }
+double cave_simt_exact_step(const double* x, const double* y, int32_t n, double psi0, double amax, int32_t* n_eval) {
+  int ne = 0;
+  const double a = cave_ops::exact_step_driver(x, y, n, psi0, amax, &ne);
+  if (n_eval) *n_eval = ne;
+  return a;
+}
+double cave_simt_psitol(void) { return CAVE_PSITOL; }
+#endif  // CAVE_SIMT_OPS
 
 // ---- fused step (cone_step.h)
 int32_t cave_simt_step_lds_bytes(int64_t m_max, int64_t d) {  // what cave_hip_step_lds_bytes returns

@@ -262,7 +262,7 @@ def warm_cache(n):
 # compiled by g++ against a shim <hip/hip_runtime.h> in which every lane is a fiber.  TEST INFRASTRUCTURE ONLY.
 _SIMT_SRC = os.path.join(_HERE, "emul", "simt_abi.cpp")
 _SIMT_DEPS = _DEPS + [_SIMT_SRC, os.path.join(_HERE, "emul", "simt", "hip", "hip_runtime.h"),
-                      os.path.join(_HERE, "prims", "prim_entries.h")] + [
+                      os.path.join(_HERE, "prims", "prim_entries.h"), os.path.join(_HERE, "prims", "op_entries.h")] + [
     os.path.join(_HERE, "..", "cave_amd", "csrc", n) for n in ("wave_prims.h", "ctx_wave.h", "ctx_block.h", "cone_step.h")]
 
 
@@ -273,6 +273,8 @@ def build_simt(asan: bool = False, defines: tuple = (), tag: str = "") -> str:
     if os.path.exists(out) and os.path.getmtime(out) >= newest:
         return out
     flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer"] if asan else ["-O2"]
+    if not asan and not defines:  # the operators alone (tests/prims/op_entries.h) are compiled into the plain build only
+        flags.append("-DCAVE_SIMT_OPS")
     cmd = ["g++", "-std=c++17", "-fPIC", "-shared", "-w", *flags, *["-D" + x for x in defines],
            "-I" + os.path.join(_HERE, "emul", "simt"), _SIMT_SRC, "-o", out]
     subprocess.run(cmd, check=True)
@@ -352,6 +354,16 @@ class Simt:
             _p(out["status"]), _p(out["iters"]))
         assert rc == 0, rc
         return out
+
+    def op_run(self, op, ctx, pm1, cases, seed=0):
+        return op_run_host(self.lib, op, ctx, pm1, cases, seed)
+
+    def exact_step(self, x, y, psi0, amax):
+        return exact_step_host(self.lib, x, y, psi0, amax)
+
+    def psitol(self):
+        self.lib.cave_simt_psitol.restype = C.c_double
+        return float(self.lib.cave_simt_psitol())
 
     def prim_run(self, kind, H, rhs, **kw):
         """one solver alone on a batch of systems (prim_run_host)"""
@@ -487,3 +499,124 @@ def store_bandwidth(arrs, B, d):
             if cp[k + 1] > cp[k] + 1:
                 bw = max(bw, int(arrs["cvar"][cp[k + 1] - 1]) - int(arrs["cvar"][cp[k]]))
     return bw
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The operators of the Newton loop alone (tests/prims/op_entries.h): struct OpCase, the packing of a list of cases
+# into one input blob and the output buffers, and the host runner.  tests/prims/prims_lib.py runs the same blob on cuda:0.
+class OpCase(C.Structure):
+    """struct OpCase (tests/prims/op_entries.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("d", "p", "nnz", "nlong", "nteam", "mode", "flags", "n_seq", "ldh", "empty",
+                                         "n_outf", "n_out")] + [
+        ("n_in", C.c_int32 * 4), ("s", C.c_double * 4)] + [
+        (n, C.c_uint64) for n in ("mptr", "mcol", "mval", "cptr", "cvar", "cvalc", "usign", "vkind", "longrow", "teamrow",
+                                  "fin")] + [("in_", C.c_uint64 * 4), ("out", C.c_uint64), ("outf", C.c_uint64),
+                                             ("outi", C.c_uint64)]
+
+
+OP_KINDS = {n: i for i, n in enumerate((
+    "gather", "gather_st", "gather_diet", "refresh", "refresh_rb", "dphi", "dphi_rb", "update", "update_rb", "grad",
+    "grad_st", "grad_dense", "weight", "band_h", "dense_h", "epilogue", "lite_gather", "lite_grad", "lite_hess",
+    "lite_hess_ipm"))}
+OP_CTX = {"w1": 0, "b2": 1, "b4": 2, "l2": 3, "l4": 4, "solo": 5}
+OP_VIEW = (("mptr", np.uint32), ("mcol", np.uint16), ("mval", np.float32), ("cptr", np.uint32), ("cvar", np.uint16),
+           ("cvalc", np.float32), ("usign", np.uint8), ("vkind", np.uint8), ("longrow", np.uint32), ("teamrow", np.uint32),
+           ("fin", np.float32))
+
+
+def op_kind(op, ctx, pm1):
+    return (OP_KINDS[op] * len(OP_CTX) + OP_CTX[ctx]) * 2 + int(bool(pm1))
+
+
+def op_check_case(c):
+    """the index ranges the operators rely on (the kernels do not check them: a bad case must not reach the device)"""
+    d, p = int(c["d"]), int(c["p"])
+    mptr, cptr = np.asarray(c["mptr"], np.int64), np.asarray(c["cptr"], np.int64)
+    nnz = int(mptr[-1])
+    assert 1 <= d <= 32767 and 0 <= p <= 32767 and len(mptr) == p + 1 and len(cptr) == d + 1
+    assert mptr[0] == 0 and cptr[0] == 0 and (np.diff(mptr) >= 0).all() and (np.diff(cptr) >= 0).all() and cptr[-1] == nnz
+    mask = 0x7fff if c["pm1"] else 0xffff
+    assert len(c["mcol"]) == nnz and len(c["cvar"]) == nnz
+    assert nnz == 0 or ((np.asarray(c["mcol"], np.int64) & mask).max() < d and (np.asarray(c["cvar"], np.int64) & mask).max() < max(p, 1))
+    if not c["pm1"]:
+        assert len(c["mval"]) == nnz and len(c["cvalc"]) == nnz
+    assert len(c["usign"]) == d and len(c["vkind"]) == p and np.asarray(c["usign"]).max(initial=0) <= 3
+    assert all(0 <= i < p for i in c["longrow"]) and all(0 <= i < p for i in c["teamrow"])
+    assert len(c["fin"]) == 2 * d and len(c["ins"]) <= 4
+
+
+def op_pack(cases):
+    """-> (blob uint8 [n], recs: per case a dict of field -> byte offset into blob, out offsets, sizes).  Every array
+    is 16-byte aligned and padded by one element."""
+    parts, off, recs = [], 0, []
+    n_out = n_outf = 0
+
+    def put(a, dt):
+        nonlocal off
+        a = np.ascontiguousarray(a, dt).ravel()
+        b = np.concatenate([a, np.zeros(1, dt)]).view(np.uint8)
+        pad = (-len(b)) % 16
+        at = off
+        parts.append(np.concatenate([b, np.zeros(pad, np.uint8)]))
+        off += len(b) + pad
+        return at
+
+    for c in cases:
+        op_check_case(c)
+        r = {}
+        for name, dt in OP_VIEW:
+            a = c.get(name)
+            r[name] = put(a if a is not None else np.zeros(0, dt), dt)
+        r["in_"] = [put(c["ins"][i] if i < len(c["ins"]) else np.zeros(0), np.float64) for i in range(4)]
+        r["out"], r["outf"] = n_out, n_outf
+        n_out += int(c["n_out"]) + 2
+        n_outf += int(c.get("n_outf", 0)) + 2
+        recs.append(r)
+    return np.concatenate(parts), recs, n_out, n_outf
+
+
+def op_structs(cases, recs, base, out_base, outf_base, outi_base):
+    arr = (OpCase * len(cases))()
+    for i, (c, r) in enumerate(zip(cases, recs)):
+        k = arr[i]
+        k.d, k.p, k.nnz = int(c["d"]), int(c["p"]), int(np.asarray(c["mptr"])[-1])
+        k.nlong, k.nteam = len(c["longrow"]), len(c["teamrow"])
+        k.mode, k.flags, k.n_seq = int(c.get("mode", 0)), int(c.get("flags", 0)), int(c.get("n_seq", 0))
+        k.ldh, k.empty, k.n_outf, k.n_out = int(c.get("ldh", 0)), int(c.get("empty", 0)), int(c.get("n_outf", 0)), int(c["n_out"])
+        for j in range(4):
+            k.n_in[j] = len(np.ravel(c["ins"][j])) if j < len(c["ins"]) else 0
+            k.s[j] = float(c.get("s", (0, 0, 0, 0))[j])
+            k.in_[j] = base + r["in_"][j]
+        for name, _ in OP_VIEW:
+            setattr(k, name, base + r[name])
+        k.out, k.outf, k.outi = out_base + 8 * r["out"], outf_base + 4 * r["outf"], outi_base + 16 * i
+    return arr
+
+
+def op_unpack(cases, recs, out, outf, outi):
+    return [{"out": out[r["out"]:r["out"] + int(c["n_out"])].copy(),
+             "outf": outf[r["outf"]:r["outf"] + int(c.get("n_outf", 0))].copy(), "outi": outi[4 * i:4 * i + 4].copy()}
+            for i, (c, r) in enumerate(zip(cases, recs))]
+
+
+def op_run_host(lib, op, ctx, pm1, cases, seed=0):
+    """A batch of cases (dicts, tests/ops_cases.py) through cave_simt_op_run on host arrays -> per case {"out", "outf",
+    "outi"}; outputs start as NaN (out, outf) / -7 (outi), so an element that is never written is caught."""
+    assert lib.cave_simt_op_case_bytes() == C.sizeof(OpCase)
+    blob, recs, n_out, n_outf = op_pack(cases)
+    out = np.full(n_out, np.nan)
+    outf = np.full(n_outf, np.nan, np.float32)
+    outi = np.full(4 * len(cases), -7, np.int32)
+    arr = op_structs(cases, recs, blob.ctypes.data, out.ctypes.data, outf.ctypes.data, outi.ctypes.data)
+    rc = lib.cave_simt_op_run(C.c_int32(op_kind(op, ctx, pm1)), arr, C.c_int64(len(cases)), C.c_uint64(seed))
+    assert rc == 0, (rc, op, ctx, pm1)
+    return op_unpack(cases, recs, out, outf, outi)
+
+
+def exact_step_host(lib, x, y, psi0, amax):
+    """exact_step on a piecewise-linear phi' given by its breakpoints -> (alpha, evaluations)"""
+    x, y = np.ascontiguousarray(x, np.float64), np.ascontiguousarray(y, np.float64)
+    lib.cave_simt_exact_step.restype = C.c_double
+    ne = C.c_int32(0)
+    a = lib.cave_simt_exact_step(_p(x), _p(y), C.c_int32(len(x)), C.c_double(psi0), C.c_double(amax), C.byref(ne))
+    return float(a), ne.value

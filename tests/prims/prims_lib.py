@@ -17,7 +17,13 @@ _OBJ_DIR = os.path.join(_HERE, "build")
 LIB_PATH = os.path.join(_HERE, "_prims.so")
 # (object name, extra flags): the entries as the product compiles them, and the dense entries once more with the
 # two-columns-per-lane trailing update of cone_dense.h instead of the MFMA one, under the symbol suffix _nomfma
-_UNITS = (("prims", ()), ("prims_nomfma", ("-DCAVE_DENSE_NO_MFMA", "-DCAVE_PRIMS_DENSE_ONLY", "-DCAVE_PRIMS_SUFFIX=_nomfma")))
+# ... and the operators of the Newton loop (op_entries.h), a unit with a source file of its own
+_UNITS = (("prims", ()), ("prims_nomfma", ("-DCAVE_DENSE_NO_MFMA", "-DCAVE_PRIMS_DENSE_ONLY", "-DCAVE_PRIMS_SUFFIX=_nomfma")),
+          ("ops", (), "ops_abi.hip"))
+
+
+def _unit_src(unit):
+    return os.path.join(_HERE, unit[2]) if len(unit) > 2 else _SRC
 
 
 def build(verbose: bool = False) -> str:
@@ -26,23 +32,23 @@ def build(verbose: bool = False) -> str:
     from cave_amd import _lib
 
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    deps = [_SRC, os.path.join(_HERE, "prim_entries.h")] + list(_lib._HEADERS)
+    deps = [_SRC, os.path.join(_HERE, "prim_entries.h"), os.path.join(_HERE, "op_entries.h")] + [_unit_src(u) for u in _UNITS] + list(_lib._HEADERS)
     newest = max(os.path.getmtime(p) for p in deps)
     os.makedirs(_OBJ_DIR, exist_ok=True)
-    objs = [os.path.join(_OBJ_DIR, name + ".o") for name, _ in _UNITS]
-    todo = [(o, fl) for o, (_, fl) in zip(objs, _UNITS) if not os.path.exists(o) or os.path.getmtime(o) < newest]
+    objs = [os.path.join(_OBJ_DIR, u[0] + ".o") for u in _UNITS]
+    todo = [(o, u[1], _unit_src(u)) for o, u in zip(objs, _UNITS) if not os.path.exists(o) or os.path.getmtime(o) < newest]
     if not todo and os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(o) for o in objs):
         return LIB_PATH
 
     def compile_one(job):
-        obj, extra = job
+        obj, extra, src = job
         cmd = [hipcc, *_lib.HIPCC_FLAGS, "-I" + _lib._CSRC, "-I" + os.path.join(_ROOT, "include"), "-I" + _HERE, *extra,
-               "-c", _SRC, "-o", obj]
+               "-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
 
-    with ThreadPoolExecutor(max_workers=2) as ex:
+    with ThreadPoolExecutor(max_workers=3) as ex:
         list(ex.map(compile_one, todo))
     subprocess.run([hipcc, "--offload-arch=gfx950", "-fPIC", "-shared", *objs, "-o", LIB_PATH], check=True)
     return LIB_PATH
@@ -55,6 +61,10 @@ class Prims:
     def __init__(self):
         if not os.path.exists(LIB_PATH):
             raise ImportError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
+        # torch first: _prims.so then binds to the HIP runtime torch has loaded.  Loaded before torch (a test file of this
+        # tier run on its own), the library brings in a second copy of the runtime, whose calls return hipErrorNoDevice
+        import torch  # noqa: F401
+
         self.lib = C.CDLL(LIB_PATH)
         self.lib.cave_prims_info.restype = C.c_int64
 
@@ -90,3 +100,25 @@ class Prims:
         assert rc == 0, (rc, kind, p, nF, bw)
         torch.cuda.synchronize()
         return {"x": tx.cpu().numpy(), "M": tM.cpu().numpy(), "aux": taux.cpu().numpy(), "fail": tfail.cpu().numpy()}
+
+    def op_run(self, op, ctx, pm1, cases, seed=0):
+        """the contract of emul_lib.op_run_host, on cuda:0 (seed: ignored, the hardware schedules)"""
+        import torch
+
+        import emul_lib as E
+
+        dev = torch.device("cuda:0")
+        assert self.lib.cave_ops_case_bytes() == C.sizeof(E.OpCase)
+        blob, recs, n_out, n_outf = E.op_pack(cases)
+        tblob = torch.from_numpy(blob).to(dev)
+        tout = torch.full((n_out,), float("nan"), dtype=torch.float64, device=dev)
+        toutf = torch.full((max(n_outf, 1),), float("nan"), dtype=torch.float32, device=dev)
+        touti = torch.full((4 * len(cases),), -7, dtype=torch.int32, device=dev)
+        arr = E.op_structs(cases, recs, tblob.data_ptr(), tout.data_ptr(), toutf.data_ptr(), touti.data_ptr())
+        raw = np.frombuffer(bytes(arr), np.uint8)
+        tcases = torch.from_numpy(raw.copy()).to(dev)
+        rc = self.lib.cave_ops_run(C.c_int32(E.op_kind(op, ctx, pm1)), arr, C.c_void_p(tcases.data_ptr()), C.c_int64(len(cases)),
+                                   C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        assert rc == 0, (rc, op, ctx, pm1, self.lib.cave_ops_last_refusal(0), self.lib.cave_ops_last_refusal(1))
+        torch.cuda.synchronize()
+        return E.op_unpack(cases, recs, tout.cpu().numpy(), toutf.cpu().numpy(), touti.cpu().numpy())
