@@ -10,6 +10,7 @@
 #include "kernels.h"
 #include "sp_grid.h"
 #include "tsp_hk.h"
+#include "vrp_dp.h"
 
 namespace cave {
 
@@ -654,6 +655,43 @@ int32_t cave_hip_tsp_hk_solve(const float* costs, const float* eval_costs, int64
   P.ws = slot > 0 ? static_cast<double*>(workspace) : nullptr; P.slot_doubles = slot / 8;
   hipError_t e = launch_tsp_hk((unsigned)grid, (hipStream_t)stream, P);
   if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch tsp_hk kernel", e);
+  return CAVE_OK;
+}
+
+// ------------------------------------------------------------------ CVRP dynamic program (vrp_dp.h)
+
+int64_t cave_hip_vrp_dp_slot_bytes(int64_t n, int64_t K) {
+  if (!vrp_dp_valid(n, K)) return fail(CAVE_E_INVALID, "vrp_dp_slot_bytes: need 3 <= n <= 14 and 1 <= K <= 8");
+  return vrp_dp_slot_bytes(n, K);
+}
+
+int64_t cave_hip_vrp_dp_workspace_bytes(int64_t n, int64_t K, int64_t N) {
+  if (!vrp_dp_valid(n, K) || N < 0) return fail(CAVE_E_INVALID, "vrp_dp_workspace_bytes: need 3 <= n <= 14, 1 <= K <= 8 and N >= 0");
+  return vrp_dp_slot_bytes(n, K) * (N < kTspHkDefaultSlots ? N : kTspHkDefaultSlots);
+}
+
+int32_t cave_hip_vrp_dp_solve(const float* costs, const float* eval_costs, const float* demands, double capacity, int64_t K,
+                              int64_t N, int64_t n, float* sol, double* obj, double* eval, int32_t* routes, int32_t* status,
+                              void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!vrp_dp_valid(n, K)) return fail(CAVE_E_INVALID, "vrp_dp_solve: need 3 <= n <= 14 and 1 <= K <= 8");
+  if (eval && !eval_costs) return fail(CAVE_E_INVALID, "vrp_dp_solve: eval needs eval_costs");
+  if (N < 0) return fail(CAVE_E_INVALID, "vrp_dp_solve: bad N");
+  if (!(capacity > 0.0 && capacity <= 1.7976931348623157e308)) return fail(CAVE_E_INVALID, "vrp_dp_solve: capacity must be finite and positive");
+  if (N == 0) return CAVE_OK;
+  const int64_t slot = vrp_dp_slot_bytes(n, K);
+  if (slot > 0 && (!workspace || workspace_bytes < slot || ((uintptr_t)workspace & 7u) != 0u))
+    return fail(CAVE_E_INVALID, "vrp_dp_solve: this (n, K) needs an 8-byte aligned workspace of at least one slot (cave_hip_vrp_dp_slot_bytes)");
+  if (!costs || !demands) return fail(CAVE_E_INVALID, "vrp_dp_solve: costs or demands is null");
+  int64_t grid = slot > 0 ? workspace_bytes / slot : kTspHkLdsGrid;
+  if (grid > N) grid = N;
+  if (grid > ((int64_t)1 << 20)) grid = (int64_t)1 << 20;
+  VrpDpParams P;
+  P.costs = costs; P.eval_costs = eval_costs; P.demands = demands; P.capacity = capacity; P.N = N;
+  P.n = (int32_t)n; P.d = (int32_t)tsp_hk_edges(n); P.K = (int32_t)K;
+  P.sol = sol; P.obj = obj; P.eval = eval; P.routes = routes; P.status = status;
+  P.ws = slot > 0 ? static_cast<double*>(workspace) : nullptr; P.slot_doubles = slot / 8;
+  hipError_t e = launch_vrp_dp((unsigned)grid, (hipStream_t)stream, P);
+  if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch vrp_dp kernel", e);
   return CAVE_OK;
 }
 

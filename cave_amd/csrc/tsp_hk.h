@@ -98,28 +98,11 @@ __device__ inline int tsp_hk_eid(int a, int b, int n) {  // a != b
 // S with bit k (set or not) squeezed out
 __device__ inline uint32_t tsp_hk_squeeze(uint32_t S, int k) { return (S & ((1u << k) - 1u)) | ((S >> (k + 1)) << k); }
 
-// the whole workgroup: instances blockIdx.x, blockIdx.x + gridDim.x, ...; lds: tsp_hk_lds_bytes(P.n) bytes, 16-byte aligned.
-// kWs: the table lies in this workgroup's workspace slot (a template parameter, so that the table's address space is
-// known at compile time: LDS or global instructions, not flat ones)
-template <bool kWs>
-__device__ inline void tsp_hk_block(const TspHkParams& P, unsigned char* lds) {
-  const int n = P.n, d = P.d, m = n - 1;
-  const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
+// Once per workgroup (shared with vrp_dp.h): Pascal's triangle bin[p 14 + i] = C(p, i), the class offsets off[c] (numbers
+// of m-1 bits with fewer than c bits set) and the popcount-sorted list of the m-1 bit numbers.  Ends without a barrier:
+// the list is complete after the caller's next __syncthreads().
+__device__ __forceinline__ void tsp_hk_build_list(uint16_t* bin, uint16_t* off, uint16_t* list, int m, int tid, int nt) {
   const uint32_t half = 1u << (m - 1);
-  const TspHkLds L = tsp_hk_lds_layout(n);
-  double* D = reinterpret_cast<double*>(lds + L.D);
-  double* cand = reinterpret_cast<double*>(lds + L.cand);
-  double* evl = reinterpret_cast<double*>(lds + L.evl);
-  uint16_t* bin = reinterpret_cast<uint16_t*>(lds + L.bin);  // bin[p 14 + i] = C(p, i)
-  uint16_t* off = reinterpret_cast<uint16_t*>(lds + L.off);  // off[c]: numbers of m-1 bits with fewer than c bits set
-  int32_t* state = reinterpret_cast<int32_t*>(lds + L.state);
-  int32_t* tourl = reinterpret_cast<int32_t*>(lds + L.tour);
-  float* cst = reinterpret_cast<float*>(lds + L.cst);
-  float* sol = reinterpret_cast<float*>(lds + L.sol);
-  uint16_t* list = reinterpret_cast<uint16_t*>(lds + L.list);
-  double* tab = kWs ? P.ws + (size_t)blockIdx.x * (size_t)P.slot_doubles : reinterpret_cast<double*>(lds + L.tab);
-
-  // ---- once per workgroup: Pascal's triangle, the class offsets, the popcount-sorted list
   if (tid == 0) {
     for (int p = 0; p < 14; ++p)
       for (int i = 0; i < 14; ++i)
@@ -142,6 +125,66 @@ __device__ inline void tsp_hk_block(const TspHkParams& P, unsigned char* lds) {
     }
     list[off[i] + rank] = (uint16_t)T;
   }
+}
+
+// The table, cardinality by cardinality (shared with vrp_dp.h); tab in LDS or global memory, its address space known
+// where this is inlined.  Ends with a barrier: the table is complete.
+__device__ __forceinline__ void tsp_hk_sweep(double* tab, const double* D, const uint16_t* list, const uint16_t* off, int n,
+                                             int tid, int nt) {
+  const int m = n - 1;
+  const uint32_t half = 1u << (m - 1);
+  for (int c = 1; c <= m; ++c) {
+    const int base = (int)off[c - 1], cnt = (int)off[c] - base;  // C(m-1, c-1)
+    const int items = m * cnt;
+    for (int it = tid; it < items; it += nt) {
+      const int j = it / cnt;
+      const uint32_t T = list[base + it - j * cnt];
+      double v;
+      if (c == 1) {
+        v = D[j + 1];
+      } else {
+        uint32_t Sp = (T & ((1u << j) - 1u)) | ((T >> j) << (j + 1));  // S \ {j}, m bits
+        const double* Dj = D + (j + 1) * n + 1;                        // Dj[k] = D[j+1][k+1] = D[k+1][j+1]
+        int k = __builtin_ctz(Sp);
+        const uint32_t S0 = Sp;
+        Sp &= Sp - 1u;
+        v = tab[(uint32_t)k * half + tsp_hk_squeeze(S0, k)] + Dj[k];
+        while (Sp) {
+          k = __builtin_ctz(Sp);
+          Sp &= Sp - 1u;
+          const double cd = tab[(uint32_t)k * half + tsp_hk_squeeze(S0, k)] + Dj[k];
+          if (cd < v) v = cd;  // strict: the lowest k wins a tie
+        }
+      }
+      tab[(uint32_t)j * half + T] = v;
+    }
+    __syncthreads();
+  }
+}
+
+// the whole workgroup: instances blockIdx.x, blockIdx.x + gridDim.x, ...; lds: tsp_hk_lds_bytes(P.n) bytes, 16-byte aligned.
+// kWs: the table lies in this workgroup's workspace slot (a template parameter, so that the table's address space is
+// known at compile time: LDS or global instructions, not flat ones)
+template <bool kWs>
+__device__ inline void tsp_hk_block(const TspHkParams& P, unsigned char* lds) {
+  const int n = P.n, d = P.d, m = n - 1;
+  const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
+  const uint32_t half = 1u << (m - 1);
+  const TspHkLds L = tsp_hk_lds_layout(n);
+  double* D = reinterpret_cast<double*>(lds + L.D);
+  double* cand = reinterpret_cast<double*>(lds + L.cand);
+  double* evl = reinterpret_cast<double*>(lds + L.evl);
+  uint16_t* bin = reinterpret_cast<uint16_t*>(lds + L.bin);  // bin[p 14 + i] = C(p, i)
+  uint16_t* off = reinterpret_cast<uint16_t*>(lds + L.off);  // off[c]: numbers of m-1 bits with fewer than c bits set
+  int32_t* state = reinterpret_cast<int32_t*>(lds + L.state);
+  int32_t* tourl = reinterpret_cast<int32_t*>(lds + L.tour);
+  float* cst = reinterpret_cast<float*>(lds + L.cst);
+  float* sol = reinterpret_cast<float*>(lds + L.sol);
+  uint16_t* list = reinterpret_cast<uint16_t*>(lds + L.list);
+  double* tab = kWs ? P.ws + (size_t)blockIdx.x * (size_t)P.slot_doubles : reinterpret_cast<double*>(lds + L.tab);
+
+  // ---- once per workgroup: Pascal's triangle, the class offsets, the popcount-sorted list
+  tsp_hk_build_list(bin, off, list, m, tid, nt);
 
   for (int64_t b = (int64_t)blockIdx.x; b < P.N; b += (int64_t)gridDim.x) {
     const size_t row0 = (size_t)b * (size_t)d;
@@ -168,33 +211,7 @@ __device__ inline void tsp_hk_block(const TspHkParams& P, unsigned char* lds) {
     double objv = __builtin_nan("");
     if (!bad) {  // (workgroup-uniform)
       // ---- the table, cardinality by cardinality
-      for (int c = 1; c <= m; ++c) {
-        const int base = (int)off[c - 1], cnt = (int)off[c] - base;  // C(m-1, c-1)
-        const int items = m * cnt;
-        for (int it = tid; it < items; it += nt) {
-          const int j = it / cnt;
-          const uint32_t T = list[base + it - j * cnt];
-          double v;
-          if (c == 1) {
-            v = D[j + 1];
-          } else {
-            uint32_t Sp = (T & ((1u << j) - 1u)) | ((T >> j) << (j + 1));  // S \ {j}, m bits
-            const double* Dj = D + (j + 1) * n + 1;                        // Dj[k] = D[j+1][k+1] = D[k+1][j+1]
-            int k = __builtin_ctz(Sp);
-            const uint32_t S0 = Sp;
-            Sp &= Sp - 1u;
-            v = tab[(uint32_t)k * half + tsp_hk_squeeze(S0, k)] + Dj[k];
-            while (Sp) {
-              k = __builtin_ctz(Sp);
-              Sp &= Sp - 1u;
-              const double cd = tab[(uint32_t)k * half + tsp_hk_squeeze(S0, k)] + Dj[k];
-              if (cd < v) v = cd;  // strict: the lowest k wins a tie
-            }
-          }
-          tab[(uint32_t)j * half + T] = v;
-        }
-        __syncthreads();
-      }
+      tsp_hk_sweep(tab, D, list, off, n, tid, nt);
       // ---- closing edge, then the walk back: the minimum over the remaining set's end nodes, recomputed
       if (tid == 0) {
         state[1] = (int32_t)((1u << m) - 1u);

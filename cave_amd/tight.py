@@ -34,6 +34,14 @@ Held-Karp also runs on the device, one workgroup per instance (`tsp_solve_hip`; 
 and strict comparisons of `tsp_solve` in `tsp_solve`'s candidate order, so tours, edge indicators and objectives are
 equal bit for bit, ties included.  `tsp_regret(..., device=...)` uses it; without a device it does what it always did.
 The DFJ cut set (`tsp_dfj_cuts`, `TSPConeDataset`) stays on the host.
+
+Small CVRP (the reference's `vrpModel`, src/model/vrp.py:114-209: depot degree <= 2K, customer degrees = 2, lazy
+rounded-capacity cuts): the optimum comes from a dynamic program on top of the Held-Karp table (`vrp_solve`: a route
+through a customer set costs its Held-Karp path plus the closing edge, a set-partition recurrence over the subsets picks
+the routes), the cuts from the rule of the reference's callback applied to the successive optima of the cut relaxation
+(`vrp_rcc_cuts`), the tight rows as for the TSP (`vrp_tight_normals`).  The dynamic program also runs on the device, one
+workgroup per instance (`vrp_solve_hip`; cave_amd/csrc/vrp_dp.h), bit for bit; `VRPConeDataset(..., device=...)` and
+`vrp_regret(..., device=...)` use it.  The cut loop stays on the host.
 """
 
 from __future__ import annotations
@@ -43,7 +51,8 @@ import numpy as np
 from .synth import sp_arcs
 
 __all__ = ["sp_solve", "sp_tight_normals", "sp_gen_data", "SPConeDataset", "sp_regret", "sp_solve_hip", "sp_cones_hip",
-           "tsp_solve", "tsp_dfj_cuts", "tsp_tight_normals", "tsp_gen_data", "TSPConeDataset", "tsp_regret", "tsp_solve_hip"]
+           "tsp_solve", "tsp_dfj_cuts", "tsp_tight_normals", "tsp_gen_data", "TSPConeDataset", "tsp_regret", "tsp_solve_hip",
+           "vrp_solve", "vrp_rcc_cuts", "vrp_tight_normals", "vrp_gen_data", "VRPConeDataset", "vrp_regret", "vrp_solve_hip"]
 
 
 def sp_solve(cost: np.ndarray, h: int, w: int):
@@ -233,9 +242,10 @@ def _edge_index(n: int):
     return edges, eid
 
 
-def tsp_solve(cost: np.ndarray, n: int):
-    """Optimal tour of the symmetric TSP with edge costs `cost` (lexicographic (i<j) order, d = n(n-1)/2) by
-    the Held-Karp dynamic program.  Returns (sol (d,) float32 0/1 edge indicator, objective, tour list)."""
+def _held_karp(cost: np.ndarray, n: int):
+    """The Held-Karp table of `tsp_solve` and `vrp_solve`: -> (edges, eid, D, dp, parent).  dp[S, j] is the cheapest path
+    from the depot through the customer set S (node j+1 is bit j) that ends in j; parent[S, j] its last-but-one node
+    (lowest index on a tie, np.argmin's rule), -1 where the path is the single edge from the depot."""
     if n > 14:
         raise ValueError("Held-Karp is meant for n <= 14 here (2^n n^2 work and memory)")
     edges, eid = _edge_index(n)
@@ -264,16 +274,30 @@ def tsp_solve(cost: np.ndarray, n: int):
             if best[j] < dp[nm, j]:
                 dp[nm, j] = best[j]
                 parent[nm, j] = best_k[j]
-    last = dp[full - 1] + D[1:, 0]
+    return edges, eid, D, dp, parent
+
+
+def _hk_walk(D, dp, parent, mask: int):
+    """Close the cheapest path through the customer set `mask` at the depot and walk it back: -> (cost with the closing
+    edge, nodes from the closing edge's end back to the first customer).  First minimum over the end nodes."""
+    last = dp[mask] + D[1:, 0]
     j = int(np.argmin(last))
     obj = float(last[j])
-    tour, mask = [], full - 1
+    walk = []
     while j >= 0:
-        tour.append(j + 1)
+        walk.append(j + 1)
         pj = int(parent[mask, j])
         mask ^= 1 << j
         j = pj
-    tour = [0] + tour[::-1]
+    return obj, walk
+
+
+def tsp_solve(cost: np.ndarray, n: int):
+    """Optimal tour of the symmetric TSP with edge costs `cost` (lexicographic (i<j) order, d = n(n-1)/2) by
+    the Held-Karp dynamic program.  Returns (sol (d,) float32 0/1 edge indicator, objective, tour list)."""
+    edges, eid, D, dp, parent = _held_karp(cost, n)
+    obj, walk = _hk_walk(D, dp, parent, (1 << (n - 1)) - 1)
+    tour = [0] + walk[::-1]
     sol = np.zeros(len(edges), dtype=np.float32)
     for a, b in zip(tour, tour[1:] + tour[:1]):
         sol[eid[a, b]] = 1.0
@@ -468,4 +492,314 @@ def tsp_regret(pred_costs: np.ndarray, true_costs: np.ndarray, true_objs: np.nda
     for cp, c, z in zip(pred_costs, true_costs, true_objs):
         s, _, _ = tsp_solve(cp, n)
         loss += float(c @ s) - float(z)
+    return loss / float(np.abs(true_objs).sum() + 1e-7)
+
+
+# ------------------------------------------------------------------ small CVRP (2-degree model, rounded-capacity cuts)
+
+def _vrp_tables(cost: np.ndarray, n: int, demands, capacity: float, num_vehicle: int):
+    """The tables of `vrp_solve`: Held-Karp, r(S) (the cheapest feasible route through S; +inf otherwise) and the layers
+    g_k(S) (the cheapest partition of S into exactly k feasible routes) with their argmins."""
+    edges, eid, D, dp, parent = _held_karp(cost, n)
+    m = n - 1
+    full = 1 << m
+    q = np.asarray(demands).reshape(-1)
+    if len(q) != m:
+        raise ValueError(f"vrp_solve: {m} customers, {len(q)} demands")
+    # load(S): the fp64 sum of q_j over j in S, ascending j, from 0.0 -- the highest bit is added last
+    load = np.zeros(full)
+    for j in range(m):
+        load[1 << j:2 << j] = load[:1 << j] + np.float64(q[j])
+    pc = np.zeros(full, dtype=np.int64)
+    for j in range(m):
+        pc[1 << j:2 << j] = pc[:1 << j] + 1
+    feas = (pc >= 2) & (load <= capacity)
+    closed = dp + D[1:, 0][None, :]  # +inf where j is not in S
+    r = np.where(feas, closed[np.arange(full), np.argmin(closed, axis=1)], np.inf)  # first minimum over j, ascending
+    kmax = min(int(num_vehicle), m // 2)
+    layers, args = [None, r], [None, None]  # layers[k][S] = g_k(S)
+    for k in range(2, kmax + 1):
+        prev = layers[k - 1]
+        g = np.full(full, np.inf)
+        arg = np.zeros(full, dtype=np.int64)
+        for S in ([full - 1] if k == kmax else range(full)):  # the last layer is read at the full set only
+            if pc[S] < 2 * k:
+                continue
+            low = S & -S
+            subs = np.zeros(1, dtype=np.int64)  # the subsets of S without its lowest bit, in ascending order
+            rest = S ^ low
+            while rest:
+                b = rest & -rest
+                rest ^= b
+                subs = np.concatenate([subs, subs | b])
+            R = (subs | low)[:-1]  # proper subsets that hold the lowest bit, ascending
+            val = r[R] + prev[S ^ R]
+            i = int(np.argmin(val))  # first minimum; an infinite pair never beats the initial +inf
+            if val[i] < np.inf:
+                g[S], arg[S] = val[i], R[i]
+        layers.append(g)
+        args.append(arg)
+    return edges, eid, D, dp, parent, layers, args, kmax
+
+
+def vrp_solve(cost: np.ndarray, n: int, demands, capacity: float, num_vehicle: int):
+    """Optimal solution of the CVRP of the reference's `vrpModel` (src/model/vrp.py): node 0 the depot, customers 1..n-1
+    with `demands` (n-1,), at most `num_vehicle` depot-anchored routes of at least two customers each (the reference
+    excludes single-customer routes so that x stays binary), every route's load <= capacity, every customer on one route.
+    Exact, by dynamic programming: a route through the customer set R costs the Held-Karp path through R plus the closing
+    edge; a set-partition recurrence over the subsets picks the routes.
+
+    Returns (sol (d,) float32 0/1 edge indicator, objective, routes), each route `[0, customers..., 0]`, routes in order
+    of their lowest customer.  Ties: the first minimum everywhere -- fewest routes, then the numerically smallest
+    customer set for the route of the lowest customer, then Held-Karp's rule inside a route.  With one vehicle and
+    infinite capacity this is `tsp_solve`, bit for bit.  Raises ValueError where no feasible partition exists."""
+    edges, eid, D, dp, parent, layers, args, kmax = _vrp_tables(cost, n, demands, capacity, num_vehicle)
+    full = (1 << (n - 1)) - 1
+    best, obj = 0, np.inf
+    for k in range(1, kmax + 1):
+        if layers[k][full] < obj:  # strict: the fewest routes win a tie
+            best, obj = k, layers[k][full]
+    if best == 0:
+        raise ValueError("vrp_solve: the instance is infeasible (no partition into feasible routes)")
+    routes, S = [], full
+    for k in range(best, 0, -1):
+        R = int(args[k][S]) if k > 1 else S
+        routes.append([0] + _hk_walk(D, dp, parent, R)[1][::-1] + [0])
+        S ^= R
+    sol = np.zeros(len(edges), dtype=np.float32)
+    for rt in routes:
+        for a, b in zip(rt, rt[1:]):
+            sol[eid[a, b]] = 1.0
+    return sol, float(obj), routes
+
+
+def _cut_row(comp, eid, d: int) -> np.ndarray:
+    r = np.zeros(d)
+    for a in range(len(comp)):
+        for b in range(a + 1, len(comp)):
+            r[eid[comp[a], comp[b]]] = 1.0
+    return r
+
+
+def vrp_rcc_cuts(cost: np.ndarray, n: int, demands, capacity: float, num_vehicle: int, max_rounds: int = 400):
+    """The cutting loop of the reference's `vrpModel`: solve {depot degree <= 2K, customer degrees = 2, cuts so far, x
+    binary} exactly (HiGHS), form the components of the selected customer-customer edges and give every component S of
+    three or more customers the rounded-capacity cut x(E(S)) <= |S| - ceil(q(S) / Q) -- the rule of `_vrpCallback`
+    (src/model/vrp.py:184-209), which adds the cut at every incumbent, violated or not, so each final route of three or
+    more customers carries its tight row.  One deviation: a two-customer component over capacity gets x_ab <= 0 (the
+    reference skips components below three and would accept that route).  The loop stops when no added cut is violated.
+    Meant for feasible instances (`vrp_solve` decides that first).  Returns (sol (d,) 0/1, objective, cuts), a cut being
+    (sorted customer list, right-hand side)."""
+    from scipy.optimize import Bounds, LinearConstraint, milp
+    from scipy.sparse import csr_matrix
+
+    edges, eid = _edge_index(n)
+    d = len(edges)
+    q = np.asarray(demands, dtype=np.float64).reshape(-1)
+    deg = np.zeros((n, d))
+    deg[edges[:, 0], np.arange(d)] = 1.0
+    deg[edges[:, 1], np.arange(d)] = 1.0
+    cons = [LinearConstraint(csr_matrix(deg[:1]), -np.inf, 2.0 * num_vehicle), LinearConstraint(csr_matrix(deg[1:]), 2.0, 2.0)]
+    cuts, seen = [], set()
+    cost = np.asarray(cost, dtype=np.float64)
+    for _ in range(max_rounds):
+        res = milp(cost, constraints=cons, integrality=np.ones(d), bounds=Bounds(0, 1), options={"mip_rel_gap": 0})
+        if res.status != 0:
+            raise RuntimeError(f"cut relaxation not solved (status {res.status})")
+        x = np.round(res.x)
+        parent = list(range(n))
+
+        def find(a):
+            while parent[a] != a:
+                parent[a] = parent[parent[a]]
+                a = parent[a]
+            return a
+
+        for k in np.flatnonzero(x > 0.5):
+            a, b = int(edges[k, 0]), int(edges[k, 1])
+            if a != 0:
+                parent[find(a)] = find(b)
+        comps: dict = {}
+        for v in range(1, n):
+            comps.setdefault(find(v), []).append(v)
+        violated = False
+        for comp in comps.values():
+            load = float(sum(q[v - 1] for v in comp))
+            if len(comp) >= 3:
+                rhs = float(len(comp) - int(np.ceil(load / capacity)))
+            elif len(comp) == 2 and load > capacity:
+                rhs = 0.0
+            else:
+                continue
+            key = (tuple(comp), rhs)
+            if key in seen:
+                continue
+            seen.add(key)
+            row = _cut_row(comp, eid, d)
+            cons.append(LinearConstraint(csr_matrix(row[None, :]), -np.inf, rhs))
+            cuts.append((list(comp), rhs))
+            violated = violated or float(row @ x) > rhs + 0.5
+        if not violated:
+            return x.astype(np.float32), float(cost @ x), cuts
+    raise RuntimeError("rounded-capacity cutting loop did not terminate")
+
+
+def vrp_tight_normals(sol: np.ndarray, n: int, cuts, num_vehicle: int, tol: float = 1e-5) -> np.ndarray:
+    """`_extract_tight_normals` (src/dataset.py:147-215) for the `vrpModel` at vertex `sol`.  Row order: the depot row
+    `+a` if the depot degree equals 2K (a tight `<=` row), the customer degree equalities (`+a` block then `-a` block),
+    the cuts that are tight at `sol`, `-e_k` at 0, `+e_k` at 1."""
+    edges, eid = _edge_index(n)
+    d = len(edges)
+    deg = np.zeros((n, d), dtype=np.float32)
+    deg[edges[:, 0], np.arange(d)] = 1.0
+    deg[edges[:, 1], np.arange(d)] = 1.0
+    rows = []
+    if abs(2.0 * num_vehicle - float(deg[0] @ sol)) < tol:
+        rows.append(deg[:1])
+    rows += [deg[1:], -deg[1:]]
+    lazy = []
+    for comp, rhs in cuts:
+        r = _cut_row(comp, eid, d).astype(np.float32)
+        if abs(rhs - float(r @ sol)) < tol:
+            lazy.append(r)
+    if lazy:
+        rows.append(np.asarray(lazy, dtype=np.float32))
+    low = np.where(sol <= tol)[0]
+    high = np.where((sol >= 1 - tol) & ~(sol <= tol))[0]
+    low_rows = np.zeros((len(low), d), dtype=np.float32)
+    low_rows[np.arange(len(low)), low] = -1.0
+    high_rows = np.zeros((len(high), d), dtype=np.float32)
+    high_rows[np.arange(len(high)), high] = 1.0
+    return np.vstack(rows + [low_rows, high_rows]).astype(np.float32)
+
+
+def vrp_gen_data(num_data: int, num_feat: int, n: int, deg: int = 4, noise_width: float = 0.5, seed: int = 42):
+    """Features and edge costs of `tsp_gen_data`, and one demand vector for the data set drawn as the reference's CVRP
+    test draws it (uniform on [0, 10), test/test_optmodel.py:111).  Returns (feats (N, p) float32, costs (N, d) float32,
+    demands (n-1,) float32)."""
+    feats, costs = tsp_gen_data(num_data, num_feat, n, deg=deg, noise_width=noise_width, seed=seed)
+    demands = (np.random.RandomState(seed + 7919).rand(n - 1) * 10).astype(np.float32)
+    return feats, costs, demands
+
+
+def vrp_solve_hip(costs, n: int, demands, capacity: float, num_vehicle: int, eval_costs=None):
+    """`vrp_solve` for a batch on the device: costs (N, d) float32, d = n (n-1) / 2, 3 <= n <= 14, demands (n-1,) shared
+    by the batch (taken as float32), 1 <= num_vehicle <= 8 -> (sols (N, d) float32 0/1, objs (N,) float64, routes
+    (N, n + num_vehicle) int32: `0, customers of route 1, 0, ..., 0`, then -1), equal to the host's bit for bit.  With
+    `eval_costs` (N, d) a fourth result: evals (N,) float64, the routes priced under the second cost tensor (the regret
+    numerator; the fp64 sum of their edges in route order).  Tables that do not fit the LDS lie in a workspace that is
+    allocated here for the call (at most 512 slots).  A non-finite cost, a negative or non-finite demand or an
+    infeasible instance raises ValueError."""
+    import torch
+
+    from . import _lib
+
+    lib = _lib.load()
+    n, K = int(n), int(num_vehicle)
+    if not 3 <= n <= 14:
+        raise ValueError(f"vrp_solve_hip: the dynamic program on the device takes 3 <= n <= 14 nodes, not {n}")
+    if not 1 <= K <= 8:
+        raise ValueError(f"vrp_solve_hip: 1 <= num_vehicle <= 8, not {K}")
+    capacity = float(capacity)
+    if not (np.isfinite(capacity) and capacity > 0):
+        raise ValueError("vrp_solve_hip: capacity must be finite and positive")
+    d = n * (n - 1) // 2
+    if not (isinstance(costs, torch.Tensor) and costs.is_cuda and costs.dtype == torch.float32 and costs.dim() == 2):
+        raise ValueError("vrp_solve_hip: costs must be a (N, d) float32 tensor on the device")
+    if costs.shape[1] != d:
+        raise ValueError(f"vrp_solve_hip: a CVRP on {n} nodes has {d} edges, costs has {costs.shape[1]} columns")
+    costs = costs.contiguous()
+    if eval_costs is not None:
+        if not (isinstance(eval_costs, torch.Tensor) and eval_costs.dtype == torch.float32 and eval_costs.shape == costs.shape
+                and eval_costs.device == costs.device):
+            raise ValueError("vrp_solve_hip: eval_costs must match costs in shape, dtype and device")
+        eval_costs = eval_costs.contiguous()
+    N, dev = costs.shape[0], costs.device
+    if not isinstance(demands, torch.Tensor):
+        demands = torch.from_numpy(np.array(demands, dtype=np.float32))
+    q = demands.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+    if q.numel() != n - 1:
+        raise ValueError(f"vrp_solve_hip: {n - 1} customers, {q.numel()} demands")
+    sols = torch.empty(N, d, dtype=torch.float32, device=dev)
+    objs = torch.empty(N, dtype=torch.float64, device=dev)
+    routes = torch.empty(N, n + K, dtype=torch.int32, device=dev)
+    evals = torch.empty(N, dtype=torch.float64, device=dev) if eval_costs is not None else None
+    status = torch.empty(N, dtype=torch.int32, device=dev)
+    ws_bytes = int(lib.cave_hip_vrp_dp_workspace_bytes(n, K, N))
+    if ws_bytes < 0:
+        _lib.check(ws_bytes, "cave_hip_vrp_dp_workspace_bytes")
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev) if ws_bytes else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.cave_hip_vrp_dp_solve(_lib.ptr(costs), _lib.ptr(eval_costs), _lib.ptr(q), capacity, K, N, n, _lib.ptr(sols),
+                                             _lib.ptr(objs), _lib.ptr(evals), _lib.ptr(routes), _lib.ptr(status), _lib.ptr(ws),
+                                             ws_bytes, _lib.current_stream()), "cave_hip_vrp_dp_solve")
+    if N and bool((status != _lib.ST_OK).any()):
+        b = int(torch.nonzero(status != _lib.ST_OK)[0])
+        if int(status[b]) == _lib.ST_INFEASIBLE:
+            raise ValueError(f"vrp_solve_hip: instance {b} is infeasible (no partition into feasible routes)")
+        raise ValueError(f"vrp_solve_hip: instance {b} has a non-finite cost, or a demand is negative or non-finite")
+    return (sols, objs, routes) if eval_costs is None else (sols, objs, routes, evals)
+
+
+class VRPConeDataset:
+    """`optDatasetConstrs` (src/dataset.py:26-130) for the reference's `vrpModel` without Gurobi: sols and objs from the
+    dynamic program (`vrp_solve`; on the device with `device`, `vrp_solve_hip`), cuts from the cutting loop
+    (`vrp_rcc_cuts`, host), rows those tight at the dynamic program's vertex -- a cut is a valid inequality, so it is a
+    valid generator at any vertex where it is tight.  An infeasible instance raises ValueError, as the reference does
+    without `skip_infeas`."""
+
+    def __init__(self, feats: np.ndarray, costs: np.ndarray, n: int, demands, capacity: float, num_vehicle: int, device=None):
+        import torch
+
+        self.n, self.capacity, self.num_vehicle = n, float(capacity), int(num_vehicle)
+        self.demands = np.asarray(demands, dtype=np.float32).reshape(-1)
+        costs = np.asarray(costs, dtype=np.float32)
+        if device is not None:
+            s, o, _ = vrp_solve_hip(torch.as_tensor(costs).to(torch.device(device)), n, self.demands, capacity, num_vehicle)
+            sols, objs = list(s.cpu().numpy()), [[float(v)] for v in o.cpu().numpy()]
+        else:
+            sols, objs = [], []
+            for c in costs:
+                s, o, _ = vrp_solve(c, n, self.demands, capacity, num_vehicle)
+                sols.append(s)
+                objs.append([o])
+        ctrs, ncuts = [], []
+        for c, s in zip(costs, sols):
+            cuts = vrp_rcc_cuts(c, n, self.demands, capacity, num_vehicle)[2]
+            A = vrp_tight_normals(s, n, cuts, num_vehicle)
+            ctrs.append(A)
+            ncuts.append(int(sum(abs(rhs - float(_cut_row(comp, _edge_index(n)[1], len(s)) @ s)) < 1e-5 for comp, rhs in cuts)))
+        self.feats = torch.as_tensor(feats, dtype=torch.float32)
+        self.costs = torch.as_tensor(costs, dtype=torch.float32)
+        self.sols = torch.as_tensor(np.stack(sols), dtype=torch.float32)
+        self.objs = torch.as_tensor(np.asarray(objs), dtype=torch.float32)
+        self.ctrs = [torch.as_tensor(c, dtype=torch.float32) for c in ctrs]
+        self.tight_cuts = ncuts
+
+    def __len__(self) -> int:
+        return len(self.feats)
+
+    def __getitem__(self, i: int):
+        return self.feats[i], self.costs[i], self.sols[i], self.objs[i], self.ctrs[i]
+
+
+def vrp_regret(pred_costs: np.ndarray, true_costs: np.ndarray, true_objs: np.ndarray, n: int, demands, capacity: float,
+               num_vehicle: int, device=None) -> float:
+    """Normalised regret sum(c . w(c_hat) - z*) / sum(z*) with w(.) from `vrp_solve`.
+
+    With `device`: arrays or tensors, moved to the device if they are not there; solved and priced there in one launch
+    (fp64 sums), only the scalar comes back."""
+    demands = np.asarray(demands.detach().cpu() if hasattr(demands, "detach") else demands, dtype=np.float32).reshape(-1)
+    if device is not None:
+        import torch
+
+        device = torch.device(device)
+        cp, c, z = (torch.as_tensor(t).detach().to(device=device, dtype=torch.float32) for t in (pred_costs, true_costs, true_objs))
+        evals = vrp_solve_hip(cp, n, demands, capacity, num_vehicle, eval_costs=c)[3]
+        z = z.reshape(-1).to(torch.float64)
+        return float(((evals - z).sum() / (z.abs().sum() + 1e-7)).item())
+    loss = 0.0
+    for cp, c, z in zip(pred_costs, true_costs, true_objs):
+        s, _, _ = vrp_solve(cp, n, demands, capacity, num_vehicle)
+        loss += float(c @ s) - float(np.asarray(z).reshape(-1)[0])
     return loss / float(np.abs(true_objs).sum() + 1e-7)

@@ -2,7 +2,8 @@
 """End-to-end CaVE training with `solver='hip'` — the loop of the reference's code_sample.py:23-60 (linear
 predictor, Adam lr 1e-2, CaVE+ loss), no Gurobi / PyEPO needed.  Default: the grid shortest path at
 BASELINE configs[0] sizes (5x5 grid, 100 instances, batch 32); `--problem tsp` is code_sample.py's own problem
-(DFJ TSP) at a size the Held-Karp / HiGHS tight-cone builder of cave_amd/tight.py handles exactly.
+(DFJ TSP) at a size the Held-Karp / HiGHS tight-cone builder of cave_amd/tight.py handles exactly; `--problem vrp` is the
+reference's CVRP model (2-degree rows, rounded-capacity cuts), solved by the dynamic program of the same module.
 
     python examples/train_sp_cave.py [--grid 5 5] [--num-data 100] [--batch 32] [--epochs 10] [--packed]
     python examples/train_sp_cave.py --problem tsp --nodes 10 --packed --warm-start
@@ -13,6 +14,7 @@ BASELINE configs[0] sizes (5x5 grid, 100 instances, batch 32); `--problem tsp` i
     python examples/train_sp_cave.py --problem tsp --sparse --prefetch [--warm-start]  # the fused step packs the next SPARSE batch
     python examples/train_sp_cave.py --grid 30 30 --num-data 1000 --device-data --packed --inner ipm  # SP solved, cones built and regret evaluated on the device
     python examples/train_sp_cave.py --problem tsp --nodes 12 --packed --device-regret  # the regret's Held-Karp solves run on the device
+    python examples/train_sp_cave.py --problem vrp --nodes 10 --capacity 30 --vehicles 3 --packed --device-regret --device-data  # CVRP: solved on the device
 """
 
 import argparse
@@ -37,8 +39,10 @@ def main(argv=None):
     ap.add_argument("--epochs", type=int, default=10)
     ap.add_argument("--variant", default="inner", choices=["exact", "inner", "hybrid"])
     ap.add_argument("--packed", action="store_true", help="device-resident packed cones instead of dense padding")
-    ap.add_argument("--problem", default="sp", choices=["sp", "tsp"])
-    ap.add_argument("--nodes", type=int, default=10, help="TSP size (Held-Karp: <= 14)")
+    ap.add_argument("--problem", default="sp", choices=["sp", "tsp", "vrp"])
+    ap.add_argument("--nodes", type=int, default=10, help="TSP / CVRP size, the depot included (Held-Karp: <= 14)")
+    ap.add_argument("--capacity", type=float, default=30.0, help="CVRP: vehicle capacity (demands are uniform on [0, 10))")
+    ap.add_argument("--vehicles", type=int, default=3, help="CVRP: number of vehicles")
     ap.add_argument("--inner", default="push", choices=["push", "ipm"],
                     help="CaVE+ interior point: 'push' (nnls-style: exact projection pushed towards the average normal) or "
                          "'ipm' (truncated interior-point iterate, as the reference's Clarabel max_iter=3: src/cave.py:213-214)")
@@ -60,21 +64,25 @@ def main(argv=None):
     ap.add_argument("--device-data", action="store_true",
                     help="(shortest path, with --packed or --sparse) solve the instances, build their tight cones on the sparse "
                          "wire format and evaluate the regret on the device (SPConeDataset(..., device=), sp_regret(..., "
-                         "device=)): no dense cone is ever made")
+                         "device=)): no dense cone is ever made; (CVRP) solve the data set's instances on the device "
+                         "(VRPConeDataset(..., device=)), the cut loop stays on the host")
     ap.add_argument("--device-regret", action="store_true",
-                    help="evaluate the regret on the device (tsp_regret(..., device=) / sp_regret(..., device=)): one launch "
+                    help="evaluate the regret on the device (tsp_regret / vrp_regret / sp_regret(..., device=)): one launch "
                          "solves every prediction and prices it, only the scalar comes back; the dataset and the training "
                          "loop are untouched")
     args = ap.parse_args(argv)
-    if args.device_data and (args.problem != "sp" or not (args.packed or args.sparse)):
-        ap.error("--device-data is for the shortest-path problem and needs --packed or --sparse (there are no dense cones)")
+    if args.device_data and (args.problem == "tsp" or (args.problem == "sp" and not (args.packed or args.sparse))):
+        ap.error("--device-data is for the shortest-path problem, where it needs --packed or --sparse (there are no dense "
+                 "cones), and for the CVRP")
+    sp_device = args.device_data and args.problem == "sp"
     if args.graph and (not args.packed or args.variant == "hybrid"):
         ap.error("--graph needs --packed and a variant without a per-call branch draw")
 
     from cave_amd.cave import EPO, exactConeAlignedCosine, innerConeAlignedCosine
     from cave_amd.dataset import ConeStore, PackedBatch, collate_sparse, prefetch
     from cave_amd.sparse import SparseCones
-    from cave_amd.tight import (SPConeDataset, TSPConeDataset, sp_gen_data, sp_regret, tsp_gen_data, tsp_regret)
+    from cave_amd.tight import (SPConeDataset, TSPConeDataset, VRPConeDataset, sp_gen_data, sp_regret, tsp_gen_data, tsp_regret,
+                                vrp_gen_data, vrp_regret)
     from torch.nn.utils.rnn import pad_sequence
 
     h, w = args.grid
@@ -82,6 +90,12 @@ def main(argv=None):
         feats, costs = tsp_gen_data(args.num_data, args.num_feat, args.nodes, deg=4, noise_width=0.5, seed=42)
         dataset = TSPConeDataset(feats, costs, args.nodes)
         print(f"TSP-{args.nodes}: {len(dataset)} instances, {sum(dataset.tight_cuts)} tight subtour cuts in all")
+    elif args.problem == "vrp":
+        feats, costs, demands = vrp_gen_data(args.num_data, args.num_feat, args.nodes, deg=4, noise_width=0.5, seed=42)
+        dataset = VRPConeDataset(feats, costs, args.nodes, demands, args.capacity, args.vehicles,
+                                 device="cuda" if args.device_data else None)
+        print(f"CVRP-{args.nodes - 1} (capacity {args.capacity:g}, {args.vehicles} vehicles): {len(dataset)} instances, "
+              f"{sum(dataset.tight_cuts)} tight rounded-capacity cuts in all")
     else:
         feats, costs = sp_gen_data(args.num_data, args.num_feat, h, w, deg=4, noise_width=0.5, seed=135)
         dataset = SPConeDataset(feats, costs, h, w, device="cuda" if args.device_data else None)
@@ -107,7 +121,7 @@ def main(argv=None):
         cave = innerConeAlignedCosine(_Model(), solver="hip", solve_ratio=0.3, inner_ratio=0.2, seed=0, solver_kwargs=kw or None)
 
     # --sparse: what a dataset built from a solver's sparse constraint matrix would keep -- one SparseCones per instance
-    if args.device_data:
+    if sp_device:
         sparse_ctrs = dataset.cones   # already on the device, straight from the solve kernel
     else:
         sparse_ctrs = SparseCones.from_ragged(dataset.ctrs) if args.sparse else None
@@ -123,7 +137,7 @@ def main(argv=None):
         x, c = dataset.feats[idx.to(dataset.feats.device)], dataset.costs[idx.to(dataset.costs.device)]
         if args.packed:
             return x, c, idx
-        if args.device_data:
+        if sp_device:
             return x, c, sparse_ctrs[idx]   # one gather on the device
         if args.sparse:
             return collate_sparse([(x[j], c[j], sparse_ctrs[i]) for j, i in enumerate(batch)])
@@ -181,7 +195,7 @@ def main(argv=None):
                                 generator=torch.Generator().manual_seed(0))  # the same batch order as an eager run
 
     def regret():
-        if args.device_data:  # predictions and true costs stay on the device, only the scalar comes back
+        if sp_device:  # predictions and true costs stay on the device, only the scalar comes back
             with torch.no_grad():
                 return sp_regret(reg(dataset.feats), dataset.costs, dataset.objs[:, 0], h, w, device=dev)
         if args.device_regret:  # a host dataset: costs and objectives go to the device, the predictions are there already
@@ -189,11 +203,16 @@ def main(argv=None):
                 cp = reg(dataset.feats.to(dev))
                 if args.problem == "tsp":
                     return tsp_regret(cp, dataset.costs, dataset.objs[:, 0], args.nodes, device=dev)
+                if args.problem == "vrp":
+                    return vrp_regret(cp, dataset.costs, dataset.objs[:, 0], args.nodes, demands, args.capacity, args.vehicles,
+                                      device=dev)
                 return sp_regret(cp, dataset.costs, dataset.objs[:, 0], h, w, device=dev)
         with torch.no_grad():
             cp = reg(dataset.feats.to(dev)).cpu().numpy()
         if args.problem == "tsp":
             return tsp_regret(cp, dataset.costs.numpy(), dataset.objs.numpy()[:, 0], args.nodes)
+        if args.problem == "vrp":
+            return vrp_regret(cp, dataset.costs.numpy(), dataset.objs.numpy()[:, 0], args.nodes, demands, args.capacity, args.vehicles)
         return sp_regret(cp, dataset.costs.numpy(), dataset.objs.numpy()[:, 0], h, w)
 
     hist = [(0, float("nan"), regret())]

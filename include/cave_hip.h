@@ -54,6 +54,7 @@ extern "C" {
 #define CAVE_ST_NOT_CONVERGED 1 /* iteration cap reached (SciPy raises RuntimeError, src/cave.py:307) */
 #define CAVE_ST_TOO_LARGE 2     /* cone did not fit this launch's LDS arena; retry with larger limits */
 #define CAVE_ST_BAD_INPUT 3     /* non-finite values; sparse wire format: an entry that breaks its contract */
+#define CAVE_ST_INFEASIBLE 4    /* cave_hip_vrp_dp_solve: the instance has no feasible solution */
 
 /* modes */
 #define CAVE_MODE_PROJECT 0
@@ -476,6 +477,52 @@ int64_t cave_hip_tsp_hk_workspace_bytes(int64_t n, int64_t N);
 int32_t cave_hip_tsp_hk_solve(const float* costs, const float* eval_costs, int64_t N, int64_t n, float* sol, double* obj,
                               double* eval, int32_t* tour, int32_t* status, void* workspace, int64_t workspace_bytes,
                               void* stream);
+
+/* ------------------------------------------------------------------ CVRP dynamic program (additive to v10)
+ * The capacitated vehicle routing problem of the reference's vrpModel on the edges of the Held-Karp section above: n
+ * nodes, 3 <= n <= 14, node 0 the depot, customers 1 .. n-1 with demands shared by the batch, at most K routes,
+ * 1 <= K <= 8, each depot-anchored, of at least two customers and of load <= capacity, every customer on one route.
+ * N instances, one 256-thread workgroup each, in ONE launch:
+ *   costs      [N, d] fp32   the costs the routes are optimal for
+ *   eval_costs [N, d] fp32   or NULL: a second cost tensor the routes are priced under (the regret numerator)
+ *   demands    [n-1]  fp32   demand of customer j+1 at [j]
+ *   sol        [N, d] fp32   or NULL: 0/1 edge indicator of the optimal routes
+ *   obj        [N]    fp64   or NULL: their cost under `costs`
+ *   eval       [N]    fp64   or NULL: the fp64 sum, from 0.0, of eval_costs over the routes' edges: route by route in route
+ *                            order, each route's edges from the depot out and back (needs eval_costs)
+ *   routes     [N, n+K] int32 or NULL: 0, customers of route 1, 0, customers of route 2, 0, ..., 0, then -1; routes in
+ *                            order of their lowest customer
+ *   status     [N]           or NULL: CAVE_ST_OK; CAVE_ST_BAD_INPUT for a non-finite cost (that instance alone) or a
+ *                            negative or non-finite demand (every instance); CAVE_ST_INFEASIBLE where no partition into
+ *                            feasible routes exists.  A failed instance gets a zero sol, NaN obj / eval, routes of -1.
+ *   workspace                where cave_hip_vrp_dp_slot_bytes(n, K) is 0: unused, may be NULL (the tables lie in LDS).
+ *                            Else a device buffer of workspace_bytes bytes, 8-byte aligned, at least one slot; the launch
+ *                            uses min(N, workspace_bytes / slot_bytes) workgroups, which stride over the instances.  Its
+ *                            contents on entry do not matter and mean nothing afterwards.
+ * The dynamic program in fp64 on the exactly converted fp32 inputs (customer j+1 is bit j of a set S):
+ *   dp[S, j]  the Held-Karp table above;   load(S) the sum of the demands over j in S, ascending j, from 0.0
+ *   r(S)   = min over j in S, ascending, of dp[S, j] + cost(j+1, 0) where S has two or more customers and load(S) <=
+ *            capacity (a load equal to the capacity fits), else +inf
+ *   g_1 = r;  g_k(S) = min over R containing the lowest customer of S, R a proper subset of S, in ascending numeric order
+ *            of R, of r(R) + g_(k-1)(S \ R)
+ *   obj    = min over k = 1 .. min(K, (n-1)/2), ascending, of g_k(all customers)
+ * every minimum the first one (a candidate replaces the minimum only when strictly smaller), and the routes are walked
+ * back through the same argmins: results do not depend on the batch, the launch, the workspace size or the device.
+ * With K = 1 and a capacity above the total load this is cave_hip_tsp_hk_solve.  No state between calls.
+ * N == 0: nothing to do, CAVE_OK.
+ * CAVE_E_INVALID before any launch: n or K out of range; eval without eval_costs; a capacity that is not finite and
+ * positive; with N > 0 a NULL costs or demands, or, where a slot is needed, a NULL or misaligned workspace or one
+ * smaller than one slot.
+ * Tables: the Held-Karp table, (n-1) 2^(n-2) doubles, and (min(K, (n-1)/2) - 1) 2^(n-1) doubles for r and the stored
+ * layers.  What fits the 160 KiB of LDS beside the small arrays stays there (both; else the second alone), the rest
+ * makes up the slot.  cave_hip_vrp_dp_slot_bytes: the bytes of one slot (0: none needed).
+ * cave_hip_vrp_dp_workspace_bytes: slot_bytes * min(N, 512), the default workspace.  Both return CAVE_E_INVALID for
+ * an n or K out of range (the second also for N < 0). */
+int64_t cave_hip_vrp_dp_slot_bytes(int64_t n, int64_t K);
+int64_t cave_hip_vrp_dp_workspace_bytes(int64_t n, int64_t K, int64_t N);
+int32_t cave_hip_vrp_dp_solve(const float* costs, const float* eval_costs, const float* demands, double capacity,
+                              int64_t K, int64_t N, int64_t n, float* sol, double* obj, double* eval,
+                              int32_t* routes, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
