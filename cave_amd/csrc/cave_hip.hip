@@ -10,6 +10,7 @@
 #include "kernels.h"
 #include "sp_grid.h"
 #include "tsp_hk.h"
+#include "tsp_hk_wide.h"
 #include "vrp_dp.h"
 
 namespace cave {
@@ -692,6 +693,44 @@ int32_t cave_hip_vrp_dp_solve(const float* costs, const float* eval_costs, const
   P.ws = slot > 0 ? static_cast<double*>(workspace) : nullptr; P.slot_doubles = slot / 8;
   hipError_t e = launch_vrp_dp((unsigned)grid, (hipStream_t)stream, P);
   if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch vrp_dp kernel", e);
+  return CAVE_OK;
+}
+
+// ------------------------------------------------------------------ Held-Karp TSP, 13 <= n <= 20 (tsp_hk_wide.h)
+
+int64_t cave_hip_tsp_hk_wide_slot_bytes(int64_t n) {
+  if (!tsp_hk_wide_valid_n(n)) return fail(CAVE_E_INVALID, "tsp_hk_wide_slot_bytes: need 13 <= n <= 20");
+  return tsp_hk_wide_slot_bytes(n);
+}
+
+int64_t cave_hip_tsp_hk_wide_workspace_bytes(int64_t n, int64_t N) {
+  if (!tsp_hk_wide_valid_n(n) || N < 0) return fail(CAVE_E_INVALID, "tsp_hk_wide_workspace_bytes: need 13 <= n <= 20 and N >= 0");
+  const int64_t slots = tsp_hk_wide_default_slots(n);
+  return tsp_hk_wide_header_bytes(n) + tsp_hk_wide_slot_bytes(n) * (N < slots ? N : slots);
+}
+
+int32_t cave_hip_tsp_hk_wide_solve(const float* costs, const float* eval_costs, int64_t N, int64_t n, float* sol, double* obj,
+                                   double* eval, int32_t* tour, int32_t* status, void* workspace, int64_t workspace_bytes,
+                                   void* stream) {
+  if (!tsp_hk_wide_valid_n(n)) return fail(CAVE_E_INVALID, "tsp_hk_wide_solve: need 13 <= n <= 20");
+  if (eval && !eval_costs) return fail(CAVE_E_INVALID, "tsp_hk_wide_solve: eval needs eval_costs");
+  if (N < 0) return fail(CAVE_E_INVALID, "tsp_hk_wide_solve: bad N");
+  if (N == 0) return CAVE_OK;
+  const int64_t slot = tsp_hk_wide_slot_bytes(n), header = tsp_hk_wide_header_bytes(n);
+  if (!workspace || workspace_bytes < header + slot || ((uintptr_t)workspace & 7u) != 0u)
+    return fail(CAVE_E_INVALID, "tsp_hk_wide_solve: needs an 8-byte aligned workspace of the header region and at least one slot "
+                                "(cave_hip_tsp_hk_wide_workspace_bytes)");
+  if (!costs) return fail(CAVE_E_INVALID, "tsp_hk_wide_solve: costs is null");
+  int64_t grid = (workspace_bytes - header) / slot;
+  if (grid > N) grid = N;
+  if (grid > ((int64_t)1 << 20)) grid = (int64_t)1 << 20;
+  TspHkWideParams P;
+  P.costs = costs; P.eval_costs = eval_costs; P.N = N; P.n = (int32_t)n; P.d = (int32_t)tsp_hk_wide_edges(n);
+  P.sol = sol; P.obj = obj; P.eval = eval; P.tour = tour; P.status = status;
+  P.list = static_cast<uint32_t*>(workspace);
+  P.ws = reinterpret_cast<double*>(static_cast<unsigned char*>(workspace) + header); P.slot_doubles = slot / 8;
+  hipError_t e = launch_tsp_hk_wide((unsigned)grid, (hipStream_t)stream, P);
+  if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch tsp_hk_wide kernels", e);
   return CAVE_OK;
 }
 

@@ -32,8 +32,11 @@ among them are then stacked exactly as `_extract_tight_normals` does (src/datase
 
 Held-Karp also runs on the device, one workgroup per instance (`tsp_solve_hip`; cave_amd/csrc/tsp_hk.h): the additions
 and strict comparisons of `tsp_solve` in `tsp_solve`'s candidate order, so tours, edge indicators and objectives are
-equal bit for bit, ties included.  `tsp_regret(..., device=...)` uses it; without a device it does what it always did.
-The DFJ cut set (`tsp_dfj_cuts`, `TSPConeDataset`) stays on the host.
+equal bit for bit, ties included, 3 <= n <= 14.  A second tier, written for a table in HBM, takes 13 <= n <= 20
+(`tsp_solve_hip_wide`; cave_amd/csrc/tsp_hk_wide.h: a predecessor set loads its entries once and extends them to every
+successor): the same recurrence bit for bit, beyond the 14 nodes at which the host's `tsp_solve` stops.
+`tsp_regret(..., device=...)` uses the first up to 14 nodes and the second from 15 to 20; without a device it does what
+it always did.  The DFJ cut set (`tsp_dfj_cuts`, `TSPConeDataset`) stays on the host at every size.
 
 Small CVRP (the reference's `vrpModel`, src/model/vrp.py:114-209: depot degree <= 2K, customer degrees = 2, lazy
 rounded-capacity cuts): the optimum comes from a dynamic program on top of the Held-Karp table (`vrp_solve`: a route
@@ -52,6 +55,7 @@ from .synth import sp_arcs
 
 __all__ = ["sp_solve", "sp_tight_normals", "sp_gen_data", "SPConeDataset", "sp_regret", "sp_solve_hip", "sp_cones_hip",
            "tsp_solve", "tsp_dfj_cuts", "tsp_tight_normals", "tsp_gen_data", "TSPConeDataset", "tsp_regret", "tsp_solve_hip",
+           "tsp_solve_hip_wide",
            "vrp_solve", "vrp_rcc_cuts", "vrp_tight_normals", "vrp_gen_data", "VRPConeDataset", "vrp_regret", "vrp_solve_hip"]
 
 
@@ -430,30 +434,27 @@ class TSPConeDataset:
         return self.feats[i], self.costs[i], self.sols[i], self.objs[i], self.ctrs[i]
 
 
-def tsp_solve_hip(costs, n: int, eval_costs=None):
-    """`tsp_solve` for a batch on the device: costs (N, d) float32, d = n (n-1) / 2, 3 <= n <= 14 -> (sols (N, d) float32
-    0/1, objs (N,) float64, tours (N, n) int32 starting at node 0), equal to the host's bit for bit.  With `eval_costs`
-    (N, d) a fourth result: evals (N,) float64, each tour priced under the second cost tensor (the regret numerator; the
-    fp64 sum of its n edges in tour order).  For n = 13, 14 the table of the dynamic program lies in a workspace that is
-    allocated here for the call (at most 512 slots: 101 MB, 218 MB).  A non-finite cost raises ValueError."""
+def _tsp_hk_hip(who: str, entry: str, lo: int, hi: int, costs, n: int, eval_costs):
+    """`tsp_solve_hip` and `tsp_solve_hip_wide`: the checks, the outputs, the default workspace of the C ABI entry
+    cave_hip_<entry>_solve (allocated for the call) and the launch."""
     import torch
 
     from . import _lib
 
     lib = _lib.load()
     n = int(n)
-    if not 3 <= n <= 14:
-        raise ValueError(f"tsp_solve_hip: Held-Karp on the device takes 3 <= n <= 14 nodes, not {n}")
+    if not lo <= n <= hi:
+        raise ValueError(f"{who}: Held-Karp on the device takes {lo} <= n <= {hi} nodes, not {n}")
     d = n * (n - 1) // 2
     if not (isinstance(costs, torch.Tensor) and costs.is_cuda and costs.dtype == torch.float32 and costs.dim() == 2):
-        raise ValueError("tsp_solve_hip: costs must be a (N, d) float32 tensor on the device")
+        raise ValueError(f"{who}: costs must be a (N, d) float32 tensor on the device")
     if costs.shape[1] != d:
-        raise ValueError(f"tsp_solve_hip: a TSP on {n} nodes has {d} edges, costs has {costs.shape[1]} columns")
+        raise ValueError(f"{who}: a TSP on {n} nodes has {d} edges, costs has {costs.shape[1]} columns")
     costs = costs.contiguous()
     if eval_costs is not None:
         if not (isinstance(eval_costs, torch.Tensor) and eval_costs.dtype == torch.float32 and eval_costs.shape == costs.shape
                 and eval_costs.device == costs.device):
-            raise ValueError("tsp_solve_hip: eval_costs must match costs in shape, dtype and device")
+            raise ValueError(f"{who}: eval_costs must match costs in shape, dtype and device")
         eval_costs = eval_costs.contiguous()
     N, dev = costs.shape[0], costs.device
     sols = torch.empty(N, d, dtype=torch.float32, device=dev)
@@ -461,31 +462,51 @@ def tsp_solve_hip(costs, n: int, eval_costs=None):
     tours = torch.empty(N, n, dtype=torch.int32, device=dev)
     evals = torch.empty(N, dtype=torch.float64, device=dev) if eval_costs is not None else None
     status = torch.empty(N, dtype=torch.int32, device=dev)
-    ws_bytes = int(lib.cave_hip_tsp_hk_workspace_bytes(n, N))
+    ws_bytes = int(getattr(lib, f"cave_hip_{entry}_workspace_bytes")(n, N))
     if ws_bytes < 0:
-        _lib.check(ws_bytes, "cave_hip_tsp_hk_workspace_bytes")
-    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev) if ws_bytes else None
+        _lib.check(ws_bytes, f"cave_hip_{entry}_workspace_bytes")
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev) if ws_bytes and N else None
     with torch.cuda.device(dev):
-        _lib.check(lib.cave_hip_tsp_hk_solve(_lib.ptr(costs), _lib.ptr(eval_costs), N, n, _lib.ptr(sols), _lib.ptr(objs),
-                                             _lib.ptr(evals), _lib.ptr(tours), _lib.ptr(status), _lib.ptr(ws), ws_bytes,
-                                             _lib.current_stream()), "cave_hip_tsp_hk_solve")
+        _lib.check(getattr(lib, f"cave_hip_{entry}_solve")(_lib.ptr(costs), _lib.ptr(eval_costs), N, n, _lib.ptr(sols), _lib.ptr(objs),
+                                                           _lib.ptr(evals), _lib.ptr(tours), _lib.ptr(status), _lib.ptr(ws),
+                                                           ws_bytes if ws is not None else 0, _lib.current_stream()),
+                   f"cave_hip_{entry}_solve")
     if N and bool((status != _lib.ST_OK).any()):
         b = int(torch.nonzero(status != _lib.ST_OK)[0])
-        raise ValueError(f"tsp_solve_hip: instance {b} has a non-finite cost")
+        raise ValueError(f"{who}: instance {b} has a non-finite cost")
     return (sols, objs, tours) if eval_costs is None else (sols, objs, tours, evals)
+
+
+def tsp_solve_hip(costs, n: int, eval_costs=None):
+    """`tsp_solve` for a batch on the device: costs (N, d) float32, d = n (n-1) / 2, 3 <= n <= 14 -> (sols (N, d) float32
+    0/1, objs (N,) float64, tours (N, n) int32 starting at node 0), equal to the host's bit for bit.  With `eval_costs`
+    (N, d) a fourth result: evals (N,) float64, each tour priced under the second cost tensor (the regret numerator; the
+    fp64 sum of its n edges in tour order).  For n = 13, 14 the table of the dynamic program lies in a workspace that is
+    allocated here for the call (at most 512 slots: 101 MB, 218 MB).  A non-finite cost raises ValueError."""
+    return _tsp_hk_hip("tsp_solve_hip", "tsp_hk", 3, 14, costs, n, eval_costs)
+
+
+def tsp_solve_hip_wide(costs, n: int, eval_costs=None):
+    """`tsp_solve_hip` for 13 <= n <= 20 (cave_hip_tsp_hk_wide_solve, cave_amd/csrc/tsp_hk_wide.h): the same arguments,
+    checks, results and errors, the same recurrence bit for bit -- beyond the host solver's 14 nodes, what `tsp_solve`
+    would return if it went that far.  The table always lies in a workspace that is allocated here for the call: one slot
+    of (n-1) 2^(n-2) doubles per workgroup (0.9 MB at n = 15, 39.8 MB at n = 20), min(N, 512, 8 GiB / slot) of them
+    (215 slots, 8.6 GB at n = 20), behind a 4 * 2^(n-1)-byte list."""
+    return _tsp_hk_hip("tsp_solve_hip_wide", "tsp_hk_wide", 13, 20, costs, n, eval_costs)
 
 
 def tsp_regret(pred_costs: np.ndarray, true_costs: np.ndarray, true_objs: np.ndarray, n: int, device=None) -> float:
     """Normalised regret sum(c . w(c_hat) - z*) / sum(z*) with w(.) from Held-Karp.
 
     With `device`: arrays or tensors, moved to the device if they are not there; solved and priced there in one launch
-    (fp64 sums), only the scalar comes back."""
+    (fp64 sums), only the scalar comes back.  Up to 14 nodes through `tsp_solve_hip`, 15 to 20 through
+    `tsp_solve_hip_wide`; without a device the host solver's limit of 14 nodes holds."""
     if device is not None:
         import torch
 
         device = torch.device(device)
         cp, c, z = (torch.as_tensor(t).detach().to(device=device, dtype=torch.float32) for t in (pred_costs, true_costs, true_objs))
-        evals = tsp_solve_hip(cp, n, eval_costs=c)[3]
+        evals = (tsp_solve_hip if int(n) <= 14 else tsp_solve_hip_wide)(cp, n, eval_costs=c)[3]
         z = z.reshape(-1).to(torch.float64)
         return float(((evals - z).sum() / (z.abs().sum() + 1e-7)).item())
     loss = 0.0

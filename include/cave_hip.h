@@ -524,6 +524,28 @@ int32_t cave_hip_vrp_dp_solve(const float* costs, const float* eval_costs, const
                               int64_t K, int64_t N, int64_t n, float* sol, double* obj, double* eval,
                               int32_t* routes, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ Held-Karp TSP, wide tier (additive to v10)
+ * The Held-Karp section above for 13 <= n <= 20: the same problem, arguments, outputs, recurrence (bit for bit the same
+ * results; at n = 13, 14 the bytes cave_hip_tsp_hk_solve writes) and failure semantics, with a table that always lies in
+ * the caller's workspace: one 512-thread workgroup per slot, workgroups striding over the N instances.
+ *   workspace   a device buffer of workspace_bytes bytes, 8-byte aligned: a header region of 4 * 2^(n-1) bytes (filled
+ *               on every call by a small kernel in front of the sweep, same stream) followed by slots of slot_bytes =
+ *               8 (n-1) 2^(n-2) bytes (196608 at n = 13 ... 39845888 at n = 20), at least one.  The launch uses
+ *               min(N, (workspace_bytes - header) / slot_bytes) workgroups.  Its contents on entry do not matter and
+ *               mean nothing afterwards; two calls that may run at the same time need a workspace each.
+ * No state between calls.  N == 0: nothing to do, CAVE_OK (no workspace needed).
+ * CAVE_E_INVALID before any launch, nothing written: n < 13 or n > 20; eval without eval_costs; with N > 0 a NULL or
+ * misaligned workspace or one smaller than the header region plus one slot.
+ * cave_hip_tsp_hk_wide_slot_bytes: the bytes of one slot.
+ * cave_hip_tsp_hk_wide_workspace_bytes: header + slot_bytes * min(N, slots(n)), the default workspace, with
+ * slots(n) = min(512, floor(8 GiB / slot_bytes)): 512 up to n = 18, 455 at n = 19, 215 at n = 20 -- a default, not a limit.
+ * Both return CAVE_E_INVALID for an n out of range (the second also for N < 0). */
+int64_t cave_hip_tsp_hk_wide_slot_bytes(int64_t n);
+int64_t cave_hip_tsp_hk_wide_workspace_bytes(int64_t n, int64_t N);
+int32_t cave_hip_tsp_hk_wide_solve(const float* costs, const float* eval_costs, int64_t N, int64_t n, float* sol, double* obj,
+                                   double* eval, int32_t* tour, int32_t* status, void* workspace, int64_t workspace_bytes,
+                                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
