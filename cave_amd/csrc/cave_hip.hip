@@ -602,23 +602,13 @@ int32_t cave_hip_sp_grid_lds_bytes(int64_t h, int64_t w) {
 
 int32_t cave_hip_sp_grid_solve(const float* costs, const float* eval_costs, int64_t N, int64_t h, int64_t w, float* sol,
                                double* obj, double* eval, int32_t* status, uint32_t* key, float* val, void* stream) {
-  if (h < 1 || w < 1 || h * w < 2) return fail(CAVE_E_INVALID, "sp_grid_solve: bad shape (need h, w >= 1 and h*w >= 2)");
-  const uint32_t wave_lds = sp_grid_wave_lds_bytes(h, w);
-  if (wave_lds == 0u) return fail(CAVE_E_INVALID, "sp_grid_solve: the grid does not fit the LDS (cave_hip_sp_grid_lds_bytes)");
-  const int64_t d = sp_grid_arcs(h, w);
-  if ((key == nullptr) != (val == nullptr)) return fail(CAVE_E_INVALID, "sp_grid_solve: key and val go together");
-  if (key && (d > 65535 || 2 * h * w + d > 65535))
-    return fail(CAVE_E_INVALID, "sp_grid_solve: cone output needs d <= 65535 and 2*h*w + d <= 65535 (16-bit rows and columns)");
-  if (eval && !eval_costs) return fail(CAVE_E_INVALID, "sp_grid_solve: eval needs eval_costs");
-  if (N < 0) return fail(CAVE_E_INVALID, "sp_grid_solve: bad N");
-  if (N == 0) return CAVE_OK;
-  if (!costs) return fail(CAVE_E_INVALID, "sp_grid_solve: costs is null");
-  const int waves = sp_grid_waves(wave_lds);
-  const int64_t grid = (N + waves - 1) / waves;
-  if (grid >= (int64_t)1 << 31) return fail(CAVE_E_INVALID, "sp_grid_solve: batch too large");
   SpGridParams P;
-  P.costs = costs; P.eval_costs = eval_costs; P.N = N; P.h = (int32_t)h; P.w = (int32_t)w; P.d = (int32_t)d;
-  P.wave_lds = wave_lds; P.sol = sol; P.obj = obj; P.eval = eval; P.status = status; P.key = key; P.val = val;
+  int64_t grid;
+  int waves;
+  char msg[kSolverMsg];
+  const int32_t rc = sp_grid_plan(costs, eval_costs, N, h, w, sol, obj, eval, status, key, val, &P, &grid, &waves, msg);
+  if (rc != CAVE_OK) return fail(rc, msg);
+  if (grid == 0) return CAVE_OK;
   hipError_t e = launch_sp_grid((unsigned)grid, waves, (hipStream_t)stream, P);
   if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch sp_grid_kernel", e);
   return CAVE_OK;
@@ -633,27 +623,18 @@ int64_t cave_hip_tsp_hk_slot_bytes(int64_t n) {
 
 int64_t cave_hip_tsp_hk_workspace_bytes(int64_t n, int64_t N) {
   if (!tsp_hk_valid_n(n) || N < 0) return fail(CAVE_E_INVALID, "tsp_hk_workspace_bytes: need 3 <= n <= 14 and N >= 0");
-  return tsp_hk_slot_bytes(n) * (N < kTspHkDefaultSlots ? N : kTspHkDefaultSlots);
+  return solver_workspace_bytes(0, tsp_hk_slot_bytes(n), N, kTspHkDefaultSlots);
 }
 
 int32_t cave_hip_tsp_hk_solve(const float* costs, const float* eval_costs, int64_t N, int64_t n, float* sol, double* obj,
                               double* eval, int32_t* tour, int32_t* status, void* workspace, int64_t workspace_bytes,
                               void* stream) {
-  if (!tsp_hk_valid_n(n)) return fail(CAVE_E_INVALID, "tsp_hk_solve: need 3 <= n <= 14");
-  if (eval && !eval_costs) return fail(CAVE_E_INVALID, "tsp_hk_solve: eval needs eval_costs");
-  if (N < 0) return fail(CAVE_E_INVALID, "tsp_hk_solve: bad N");
-  if (N == 0) return CAVE_OK;
-  const int64_t slot = tsp_hk_slot_bytes(n);
-  if (slot > 0 && (!workspace || workspace_bytes < slot || ((uintptr_t)workspace & 7u) != 0u))
-    return fail(CAVE_E_INVALID, "tsp_hk_solve: this n needs an 8-byte aligned workspace of at least one slot (cave_hip_tsp_hk_slot_bytes)");
-  if (!costs) return fail(CAVE_E_INVALID, "tsp_hk_solve: costs is null");
-  int64_t grid = slot > 0 ? workspace_bytes / slot : kTspHkLdsGrid;
-  if (grid > N) grid = N;
-  if (grid > ((int64_t)1 << 20)) grid = (int64_t)1 << 20;
   TspHkParams P;
-  P.costs = costs; P.eval_costs = eval_costs; P.N = N; P.n = (int32_t)n; P.d = (int32_t)tsp_hk_edges(n);
-  P.sol = sol; P.obj = obj; P.eval = eval; P.tour = tour; P.status = status;
-  P.ws = slot > 0 ? static_cast<double*>(workspace) : nullptr; P.slot_doubles = slot / 8;
+  int64_t grid;
+  char msg[kSolverMsg];
+  const int32_t rc = tsp_hk_plan(costs, eval_costs, N, n, sol, obj, eval, tour, status, workspace, workspace_bytes, &P, &grid, msg);
+  if (rc != CAVE_OK) return fail(rc, msg);
+  if (grid == 0) return CAVE_OK;
   hipError_t e = launch_tsp_hk((unsigned)grid, (hipStream_t)stream, P);
   if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch tsp_hk kernel", e);
   return CAVE_OK;
@@ -668,29 +649,19 @@ int64_t cave_hip_vrp_dp_slot_bytes(int64_t n, int64_t K) {
 
 int64_t cave_hip_vrp_dp_workspace_bytes(int64_t n, int64_t K, int64_t N) {
   if (!vrp_dp_valid(n, K) || N < 0) return fail(CAVE_E_INVALID, "vrp_dp_workspace_bytes: need 3 <= n <= 14, 1 <= K <= 8 and N >= 0");
-  return vrp_dp_slot_bytes(n, K) * (N < kTspHkDefaultSlots ? N : kTspHkDefaultSlots);
+  return solver_workspace_bytes(0, vrp_dp_slot_bytes(n, K), N, kTspHkDefaultSlots);
 }
 
 int32_t cave_hip_vrp_dp_solve(const float* costs, const float* eval_costs, const float* demands, double capacity, int64_t K,
                               int64_t N, int64_t n, float* sol, double* obj, double* eval, int32_t* routes, int32_t* status,
                               void* workspace, int64_t workspace_bytes, void* stream) {
-  if (!vrp_dp_valid(n, K)) return fail(CAVE_E_INVALID, "vrp_dp_solve: need 3 <= n <= 14 and 1 <= K <= 8");
-  if (eval && !eval_costs) return fail(CAVE_E_INVALID, "vrp_dp_solve: eval needs eval_costs");
-  if (N < 0) return fail(CAVE_E_INVALID, "vrp_dp_solve: bad N");
-  if (!(capacity > 0.0 && capacity <= 1.7976931348623157e308)) return fail(CAVE_E_INVALID, "vrp_dp_solve: capacity must be finite and positive");
-  if (N == 0) return CAVE_OK;
-  const int64_t slot = vrp_dp_slot_bytes(n, K);
-  if (slot > 0 && (!workspace || workspace_bytes < slot || ((uintptr_t)workspace & 7u) != 0u))
-    return fail(CAVE_E_INVALID, "vrp_dp_solve: this (n, K) needs an 8-byte aligned workspace of at least one slot (cave_hip_vrp_dp_slot_bytes)");
-  if (!costs || !demands) return fail(CAVE_E_INVALID, "vrp_dp_solve: costs or demands is null");
-  int64_t grid = slot > 0 ? workspace_bytes / slot : kTspHkLdsGrid;
-  if (grid > N) grid = N;
-  if (grid > ((int64_t)1 << 20)) grid = (int64_t)1 << 20;
   VrpDpParams P;
-  P.costs = costs; P.eval_costs = eval_costs; P.demands = demands; P.capacity = capacity; P.N = N;
-  P.n = (int32_t)n; P.d = (int32_t)tsp_hk_edges(n); P.K = (int32_t)K;
-  P.sol = sol; P.obj = obj; P.eval = eval; P.routes = routes; P.status = status;
-  P.ws = slot > 0 ? static_cast<double*>(workspace) : nullptr; P.slot_doubles = slot / 8;
+  int64_t grid;
+  char msg[kSolverMsg];
+  const int32_t rc = vrp_dp_plan(costs, eval_costs, demands, capacity, K, N, n, sol, obj, eval, routes, status, workspace,
+                                 workspace_bytes, &P, &grid, msg);
+  if (rc != CAVE_OK) return fail(rc, msg);
+  if (grid == 0) return CAVE_OK;
   hipError_t e = launch_vrp_dp((unsigned)grid, (hipStream_t)stream, P);
   if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch vrp_dp kernel", e);
   return CAVE_OK;
@@ -705,30 +676,18 @@ int64_t cave_hip_tsp_hk_wide_slot_bytes(int64_t n) {
 
 int64_t cave_hip_tsp_hk_wide_workspace_bytes(int64_t n, int64_t N) {
   if (!tsp_hk_wide_valid_n(n) || N < 0) return fail(CAVE_E_INVALID, "tsp_hk_wide_workspace_bytes: need 13 <= n <= 20 and N >= 0");
-  const int64_t slots = tsp_hk_wide_default_slots(n);
-  return tsp_hk_wide_header_bytes(n) + tsp_hk_wide_slot_bytes(n) * (N < slots ? N : slots);
+  return solver_workspace_bytes(tsp_hk_wide_header_bytes(n), tsp_hk_wide_slot_bytes(n), N, tsp_hk_wide_default_slots(n));
 }
 
 int32_t cave_hip_tsp_hk_wide_solve(const float* costs, const float* eval_costs, int64_t N, int64_t n, float* sol, double* obj,
                                    double* eval, int32_t* tour, int32_t* status, void* workspace, int64_t workspace_bytes,
                                    void* stream) {
-  if (!tsp_hk_wide_valid_n(n)) return fail(CAVE_E_INVALID, "tsp_hk_wide_solve: need 13 <= n <= 20");
-  if (eval && !eval_costs) return fail(CAVE_E_INVALID, "tsp_hk_wide_solve: eval needs eval_costs");
-  if (N < 0) return fail(CAVE_E_INVALID, "tsp_hk_wide_solve: bad N");
-  if (N == 0) return CAVE_OK;
-  const int64_t slot = tsp_hk_wide_slot_bytes(n), header = tsp_hk_wide_header_bytes(n);
-  if (!workspace || workspace_bytes < header + slot || ((uintptr_t)workspace & 7u) != 0u)
-    return fail(CAVE_E_INVALID, "tsp_hk_wide_solve: needs an 8-byte aligned workspace of the header region and at least one slot "
-                                "(cave_hip_tsp_hk_wide_workspace_bytes)");
-  if (!costs) return fail(CAVE_E_INVALID, "tsp_hk_wide_solve: costs is null");
-  int64_t grid = (workspace_bytes - header) / slot;
-  if (grid > N) grid = N;
-  if (grid > ((int64_t)1 << 20)) grid = (int64_t)1 << 20;
-  TspHkWideParams P;
-  P.costs = costs; P.eval_costs = eval_costs; P.N = N; P.n = (int32_t)n; P.d = (int32_t)tsp_hk_wide_edges(n);
-  P.sol = sol; P.obj = obj; P.eval = eval; P.tour = tour; P.status = status;
-  P.list = static_cast<uint32_t*>(workspace);
-  P.ws = reinterpret_cast<double*>(static_cast<unsigned char*>(workspace) + header); P.slot_doubles = slot / 8;
+  TspHkParams P;
+  int64_t grid;
+  char msg[kSolverMsg];
+  const int32_t rc = tsp_hk_wide_plan(costs, eval_costs, N, n, sol, obj, eval, tour, status, workspace, workspace_bytes, &P, &grid, msg);
+  if (rc != CAVE_OK) return fail(rc, msg);
+  if (grid == 0) return CAVE_OK;
   hipError_t e = launch_tsp_hk_wide((unsigned)grid, (hipStream_t)stream, P);
   if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch tsp_hk_wide kernels", e);
   return CAVE_OK;

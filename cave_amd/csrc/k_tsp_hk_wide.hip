@@ -12,17 +12,17 @@ __global__ __launch_bounds__(kTspHkWideListThreads) void tsp_hk_wide_list_kernel
 }
 
 template <int M>
-__global__ __launch_bounds__(kTspHkWideThreads) void tsp_hk_wide_kernel(TspHkWideParams P) {
+__global__ __launch_bounds__(kTspHkWideThreads) void tsp_hk_wide_kernel(TspHkParams P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   tsp_hk_wide_block<M>(P, smem);
 }
 
 template <int M>
-static void launch_m(unsigned grid, size_t lds, hipStream_t stream, const TspHkWideParams& P) {
+static void launch_m(unsigned grid, size_t lds, hipStream_t stream, const TspHkParams& P) {
   hipLaunchKernelGGL(tsp_hk_wide_kernel<M>, dim3(grid), dim3((unsigned)kTspHkWideThreads), lds, stream, P);
 }
 
-hipError_t launch_tsp_hk_wide(unsigned grid, hipStream_t stream, const TspHkWideParams& P) {
+hipError_t launch_tsp_hk_wide(unsigned grid, hipStream_t stream, const TspHkParams& P) {
   const int m = P.n - 1;
   const unsigned total = 1u << m, per = (unsigned)kTspHkWideListThreads;
   hipLaunchKernelGGL(tsp_hk_wide_list_kernel, dim3((total + per - 1u) / per), dim3(per), 0, stream, P.list, m);

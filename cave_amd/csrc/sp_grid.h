@@ -27,6 +27,7 @@
 
 #include "../../include/cave_hip.h"
 #include "cone_common.h"
+#include "solver_entry.h"
 #include "wave_prims.h"
 
 namespace cave {
@@ -62,6 +63,32 @@ CAVE_HOSTDEV int sp_grid_waves(uint32_t wave_lds) {
   int wpb = 4;
   while (wpb > 1 && (uint32_t)wpb * wave_lds > kSpGridMaxLds) wpb >>= 1;
   return wpb;
+}
+
+// cave_hip_sp_grid_solve: its checks, its grid, the waves per workgroup and its parameter block (solver_entry.h)
+inline int32_t sp_grid_plan(const float* costs, const float* eval_costs, int64_t N, int64_t h, int64_t w, float* sol, double* obj,
+                            double* eval, int32_t* status, uint32_t* key, float* val, SpGridParams* P, int64_t* grid, int* waves,
+                            char* msg) {
+  const bool shape = h >= 1 && w >= 1 && h * w >= 2;
+  const uint32_t wave_lds = shape ? sp_grid_wave_lds_bytes(h, w) : 0u;
+  const int64_t d = shape ? sp_grid_arcs(h, w) : 0;
+  const char* bad = nullptr;
+  if (!shape) bad = "bad shape (need h, w >= 1 and h*w >= 2)";
+  else if (wave_lds == 0u) bad = "the grid does not fit the LDS (cave_hip_sp_grid_lds_bytes)";
+  else if ((key == nullptr) != (val == nullptr)) bad = "key and val go together";
+  else if (key && (d > 65535 || 2 * h * w + d > 65535)) bad = "cone output needs d <= 65535 and 2*h*w + d <= 65535 (16-bit rows and columns)";
+  const int32_t rc = solver_plan("sp_grid_solve", bad, eval && !eval_costs, N, nullptr, 0, 0, nullptr, nullptr, 0,
+                                 costs ? nullptr : "costs is null", 1, grid, msg);
+  if (rc != CAVE_OK || *grid == 0) return rc;
+  *waves = sp_grid_waves(wave_lds);  // one wave per instance: the grid is the batch's workgroups, not the shared rule's
+  *grid = (N + *waves - 1) / *waves;
+  if (*grid >= (int64_t)1 << 31) {
+    snprintf(msg, kSolverMsg, "sp_grid_solve: batch too large");
+    return CAVE_E_INVALID;
+  }
+  P->costs = costs; P->eval_costs = eval_costs; P->N = N; P->h = (int32_t)h; P->w = (int32_t)w; P->d = (int32_t)d;
+  P->wave_lds = wave_lds; P->sol = sol; P->obj = obj; P->eval = eval; P->status = status; P->key = key; P->val = val;
+  return CAVE_OK;
 }
 
 #if defined(CAVE_GPU_CODE)

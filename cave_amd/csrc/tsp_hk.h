@@ -29,6 +29,7 @@
 
 #include "../../include/cave_hip.h"
 #include "cone_common.h"
+#include "solver_entry.h"
 
 namespace cave {
 
@@ -42,6 +43,7 @@ struct TspHkParams {
   double* eval;             // [N] or null
   int32_t* tour;            // [N, n] or null
   int32_t* status;          // [N] or null
+  uint32_t* list;           // wide tier (tsp_hk_wide.h): the popcount-sorted list in the workspace's header region; else null
   double* ws;               // global tier: gridDim.x slots of slot_doubles doubles; LDS tier: null
   int64_t slot_doubles;
 };
@@ -90,6 +92,30 @@ CAVE_HOSTDEV uint32_t tsp_hk_lds_bytes(int64_t n) {
   return tsp_hk_lds_layout(n).tab + (tsp_hk_in_lds(n) ? (uint32_t)tsp_hk_table_bytes(n) : 0u);
 }
 
+// The fields both Held-Karp tiers and the CVRP fill alike: the tensors, the sizes and the workspace behind its header
+template <class Params>
+inline void tsp_hk_fill(Params* P, const float* costs, const float* eval_costs, int64_t N, int64_t n, float* sol, double* obj,
+                        double* eval, int32_t* status, void* workspace, int64_t header, int64_t slot) {
+  P->costs = costs; P->eval_costs = eval_costs; P->N = N; P->n = (int32_t)n; P->d = (int32_t)tsp_hk_edges(n);
+  P->sol = sol; P->obj = obj; P->eval = eval; P->status = status;
+  P->ws = slot > 0 ? reinterpret_cast<double*>(static_cast<unsigned char*>(workspace) + header) : nullptr;
+  P->slot_doubles = slot / 8;
+}
+// cave_hip_tsp_hk_solve: its checks, its grid and its parameter block (solver_entry.h)
+inline int32_t tsp_hk_plan(const float* costs, const float* eval_costs, int64_t N, int64_t n, float* sol, double* obj, double* eval,
+                           int32_t* tour, int32_t* status, void* workspace, int64_t workspace_bytes, TspHkParams* P, int64_t* grid,
+                           char* msg) {
+  const bool valid = tsp_hk_valid_n(n);
+  const int64_t slot = valid ? tsp_hk_slot_bytes(n) : 0;
+  const int32_t rc = solver_plan("tsp_hk_solve", valid ? nullptr : "need 3 <= n <= 14", eval && !eval_costs, N, nullptr, 0, slot,
+                                 "this n needs an 8-byte aligned workspace of at least one slot (cave_hip_tsp_hk_slot_bytes)",
+                                 workspace, workspace_bytes, costs ? nullptr : "costs is null", kTspHkLdsGrid, grid, msg);
+  if (rc != CAVE_OK || *grid == 0) return rc;
+  tsp_hk_fill(P, costs, eval_costs, N, n, sol, obj, eval, status, workspace, 0, slot);
+  P->tour = tour; P->list = nullptr;
+  return CAVE_OK;
+}
+
 #if defined(CAVE_GPU_CODE)
 __device__ inline int tsp_hk_eid(int a, int b, int n) {  // a != b
   const int i = a < b ? a : b, j = a < b ? b : a;
@@ -97,6 +123,22 @@ __device__ inline int tsp_hk_eid(int a, int b, int n) {  // a != b
 }
 // S with bit k (set or not) squeezed out
 __device__ inline uint32_t tsp_hk_squeeze(uint32_t S, int k) { return (S & ((1u << k) - 1u)) | ((S >> (k + 1)) << k); }
+
+// Combinatorial number system: the rank of T among the numbers with its popcount (-> *pop); bin[p stride + i] = C(p, i)
+// (shared with tsp_hk_wide.h, whose binomials are wider)
+template <class B>
+__device__ __forceinline__ uint32_t hk_rank(uint32_t T, const B* bin, int stride, int* pop) {
+  uint32_t rank = 0u;
+  int i = 0;
+  while (T) {
+    const int p = __builtin_ctz(T);
+    T &= T - 1u;
+    ++i;
+    rank += bin[p * stride + i];
+  }
+  *pop = i;
+  return rank;
+}
 
 // Once per workgroup (shared with vrp_dp.h): Pascal's triangle bin[p 14 + i] = C(p, i), the class offsets off[c] (numbers
 // of m-1 bits with fewer than c bits set) and the popcount-sorted list of the m-1 bit numbers.  Ends without a barrier:
@@ -115,14 +157,8 @@ __device__ __forceinline__ void tsp_hk_build_list(uint16_t* bin, uint16_t* off, 
   }
   __syncthreads();
   for (uint32_t T = (uint32_t)tid; T < half; T += (uint32_t)nt) {
-    uint32_t rank = 0u, bits = T;
-    int i = 0;
-    while (bits) {  // combinatorial number system: the rank of T among the numbers with its popcount
-      const int p = __builtin_ctz(bits);
-      bits &= bits - 1u;
-      ++i;
-      rank += bin[p * 14 + i];
-    }
+    int i;
+    const uint32_t rank = hk_rank(T, bin, 14, &i);
     list[off[i] + rank] = (uint16_t)T;
   }
 }

@@ -27,27 +27,9 @@
 // built once per call by a kernel of its own in front of the sweep (same stream), each number placed by its rank in the
 // combinatorial number system: no atomics, no order dependence, never in LDS.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include "../../include/cave_hip.h"
-#include "cone_common.h"
+#include "tsp_hk.h"
 
 namespace cave {
-
-struct TspHkWideParams {
-  const float* costs;       // [N, d]
-  const float* eval_costs;  // [N, d] or null
-  int64_t N;
-  int32_t n, d;
-  float* sol;               // [N, d] or null
-  double* obj;              // [N] or null
-  double* eval;             // [N] or null
-  int32_t* tour;            // [N, n] or null
-  int32_t* status;          // [N] or null
-  uint32_t* list;           // header region: the popcount-sorted list of the (n-1)-bit numbers
-  double* ws;               // gridDim.x slots of slot_doubles doubles
-  int64_t slot_doubles;
-};
 
 static constexpr int kTspHkWideMinN = 13, kTspHkWideMaxN = 20;
 static constexpr int kTspHkWideThreads = 512;
@@ -56,10 +38,8 @@ static constexpr int64_t kTspHkWideMaxSlots = 512;                   // default 
 static constexpr int64_t kTspHkWideMaxBytes = (int64_t)8 << 30;      // ... and at most 8 GiB of them
 
 CAVE_HOSTDEV bool tsp_hk_wide_valid_n(int64_t n) { return n >= kTspHkWideMinN && n <= kTspHkWideMaxN; }
-CAVE_HOSTDEV uint32_t tsp_hk_wide_r16(uint32_t x) { return (x + 15u) & ~15u; }
-CAVE_HOSTDEV int64_t tsp_hk_wide_edges(int64_t n) { return n * (n - 1) / 2; }
 // bytes of one slot: the table, (n-1) 2^(n-2) doubles
-CAVE_HOSTDEV int64_t tsp_hk_wide_slot_bytes(int64_t n) { return 8 * (n - 1) * ((int64_t)1 << (n - 2)); }
+CAVE_HOSTDEV int64_t tsp_hk_wide_slot_bytes(int64_t n) { return tsp_hk_table_bytes(n); }
 // bytes of the header region: the list, 2^(n-1) u32
 CAVE_HOSTDEV int64_t tsp_hk_wide_header_bytes(int64_t n) { return 4 * ((int64_t)1 << (n - 1)); }
 // slots of the default workspace: min(512, floor(8 GiB / slot_bytes))
@@ -78,29 +58,38 @@ CAVE_HOSTDEV TspHkWideLds tsp_hk_wide_lds_layout(int64_t n) {
   TspHkWideLds L;
   const int64_t m = n - 1;
   uint32_t p = 0u;
-  L.D = p;     p += tsp_hk_wide_r16((uint32_t)(8 * n * n));
-  L.Dm = p;    p += tsp_hk_wide_r16((uint32_t)(8 * m * (m | 1)));
+  L.D = p;     p += tsp_hk_r16((uint32_t)(8 * n * n));
+  L.Dm = p;    p += tsp_hk_r16((uint32_t)(8 * m * (m | 1)));
   L.cand = p;  p += 256u;
   L.evl = p;   p += 256u;
   L.off = p;   p += 128u;
   L.state = p; p += 64u;
   L.tour = p;  p += 128u;
-  L.cst = p;   p += tsp_hk_wide_r16((uint32_t)(4 * tsp_hk_wide_edges(n)));
-  L.sol = p;   p += tsp_hk_wide_r16((uint32_t)(4 * tsp_hk_wide_edges(n)));
+  L.cst = p;   p += tsp_hk_r16((uint32_t)(4 * tsp_hk_edges(n)));
+  L.sol = p;   p += tsp_hk_r16((uint32_t)(4 * tsp_hk_edges(n)));
   L.end = p;
   return L;
 }
 CAVE_HOSTDEV uint32_t tsp_hk_wide_lds_bytes(int64_t n) { return tsp_hk_wide_lds_layout(n).end; }
 static constexpr uint32_t kTspHkWideListLds = 4u * 20u * 20u;  // the list kernel: Pascal's triangle, bin[p 20 + i] = C(p, i)
 
-#if defined(CAVE_GPU_CODE)
-__device__ inline int tsp_hk_wide_eid(int a, int b, int n) {  // a != b
-  const int i = a < b ? a : b, j = a < b ? b : a;
-  return i * n - i * (i + 1) / 2 + j - i - 1;
+// cave_hip_tsp_hk_wide_solve: its checks, its grid and its parameter block (solver_entry.h)
+inline int32_t tsp_hk_wide_plan(const float* costs, const float* eval_costs, int64_t N, int64_t n, float* sol, double* obj,
+                                double* eval, int32_t* tour, int32_t* status, void* workspace, int64_t workspace_bytes,
+                                TspHkParams* P, int64_t* grid, char* msg) {
+  const bool valid = tsp_hk_wide_valid_n(n);
+  const int64_t slot = valid ? tsp_hk_wide_slot_bytes(n) : 0, header = valid ? tsp_hk_wide_header_bytes(n) : 0;
+  const int32_t rc = solver_plan("tsp_hk_wide_solve", valid ? nullptr : "need 13 <= n <= 20", eval && !eval_costs, N, nullptr, header,
+                                 slot, "needs an 8-byte aligned workspace of the header region and at least one slot "
+                                 "(cave_hip_tsp_hk_wide_workspace_bytes)",
+                                 workspace, workspace_bytes, costs ? nullptr : "costs is null", kTspHkLdsGrid, grid, msg);
+  if (rc != CAVE_OK || *grid == 0) return rc;
+  tsp_hk_fill(P, costs, eval_costs, N, n, sol, obj, eval, status, workspace, header, slot);
+  P->tour = tour; P->list = static_cast<uint32_t*>(workspace);
+  return CAVE_OK;
 }
-// S with bit k (set or not) squeezed out
-__device__ inline uint32_t tsp_hk_wide_squeeze(uint32_t S, int k) { return (S & ((1u << k) - 1u)) | ((S >> (k + 1)) << k); }
 
+#if defined(CAVE_GPU_CODE)
 // The list kernel's workgroup: the m-bit numbers blockIdx.x blockDim.x + threadIdx.x, + gridDim.x blockDim.x, ..., each
 // placed behind the numbers of fewer bits (class offset) at its rank among the numbers of its popcount.
 // lds: kTspHkWideListLds bytes.
@@ -113,14 +102,8 @@ __device__ inline void tsp_hk_wide_list_block(uint32_t* list, int m, unsigned ch
   __syncthreads();
   const uint32_t total = 1u << m, stride = (uint32_t)gridDim.x * (uint32_t)blockDim.x;
   for (uint32_t T = (uint32_t)blockIdx.x * (uint32_t)blockDim.x + (uint32_t)threadIdx.x; T < total; T += stride) {
-    uint32_t rank = 0u, bits = T;
-    int i = 0;
-    while (bits) {  // combinatorial number system: the rank of T among the numbers with its popcount
-      const int p = __builtin_ctz(bits);
-      bits &= bits - 1u;
-      ++i;
-      rank += bin[p * 20 + i];
-    }
+    int i;
+    const uint32_t rank = hk_rank(T, bin, 20, &i);
     uint32_t base = 0u;  // numbers of m bits with fewer than i bits set
     for (int c = 0; c < i; ++c) base += bin[m * 20 + c];
     list[base + rank] = T;
@@ -151,7 +134,7 @@ __device__ __forceinline__ void tsp_hk_wide_sweep(double* __restrict__ tab, cons
           const int k = __builtin_ctz(bits);
           bits &= bits - 1u;
           kq[i] = k;
-          x[i] = tab[(size_t)k * half + tsp_hk_wide_squeeze(Sp, k)];
+          x[i] = tab[(size_t)k * half + tsp_hk_squeeze(Sp, k)];
         }
       double acc[M];
 #pragma unroll
@@ -168,7 +151,7 @@ __device__ __forceinline__ void tsp_hk_wide_sweep(double* __restrict__ tab, cons
         }
 #pragma unroll
       for (int j = 0; j < M; ++j)
-        if (!((Sp >> j) & 1u)) tab[(size_t)j * half + tsp_hk_wide_squeeze(Sp, j)] = acc[j];
+        if (!((Sp >> j) & 1u)) tab[(size_t)j * half + tsp_hk_squeeze(Sp, j)] = acc[j];
     }
     __syncthreads();
   }
@@ -177,7 +160,7 @@ __device__ __forceinline__ void tsp_hk_wide_sweep(double* __restrict__ tab, cons
 // the whole workgroup: instances blockIdx.x, blockIdx.x + gridDim.x, ...; lds: tsp_hk_wide_lds_bytes(P.n) bytes, 16-byte
 // aligned; P.n == M + 1; P.list complete (the list kernel ran before this one).
 template <int M>
-__device__ inline void tsp_hk_wide_block(const TspHkWideParams& P, unsigned char* lds) {
+__device__ inline void tsp_hk_wide_block(const TspHkParams& P, unsigned char* lds) {
   constexpr int n = M + 1, m = M, ms = M | 1;
   constexpr uint32_t half = 1u << (M - 1);
   const int d = P.d;
@@ -223,7 +206,7 @@ __device__ inline void tsp_hk_wide_block(const TspHkWideParams& P, unsigned char
     const bool bad = state[0] != 0;
     for (int e = tid; e < n * n; e += nt) {
       const int a = e / n, c = e - a * n;
-      const double v = a == c ? 0.0 : (double)cst[tsp_hk_wide_eid(a, c, n)];
+      const double v = a == c ? 0.0 : (double)cst[tsp_hk_eid(a, c, n)];
       D[e] = v;
       if (a >= 1 && c >= 1) Dm[(a - 1) * ms + c - 1] = v;
     }
@@ -244,7 +227,7 @@ __device__ inline void tsp_hk_wide_block(const TspHkWideParams& P, unsigned char
         const uint32_t S = (uint32_t)state[1];
         const int jn = state[2];  // the node the path continues to (0: the depot, the closing edge)
         if (tid < m && ((S >> tid) & 1u))
-          cand[tid] = tab[(size_t)tid * half + tsp_hk_wide_squeeze(S, tid)] + D[(tid + 1) * n + jn];
+          cand[tid] = tab[(size_t)tid * half + tsp_hk_squeeze(S, tid)] + D[(tid + 1) * n + jn];
         __syncthreads();
         if (tid == 0) {
           uint32_t bits = S;
@@ -268,7 +251,7 @@ __device__ inline void tsp_hk_wide_block(const TspHkWideParams& P, unsigned char
       }
       // ---- the tour's n edges: the 0/1 solution, and the edges priced in tour order
       if (tid < n) {
-        const int k = tsp_hk_wide_eid(tourl[tid], tourl[tid + 1 < n ? tid + 1 : 0], n);
+        const int k = tsp_hk_eid(tourl[tid], tourl[tid + 1 < n ? tid + 1 : 0], n);
         sol[k] = 1.0f;
         if (P.eval) evl[tid] = (double)CAVE_NT_LOAD_F32(P.eval_costs + row0 + k);
       }
@@ -297,7 +280,7 @@ __device__ inline void tsp_hk_wide_block(const TspHkWideParams& P, unsigned char
 
 #if defined(__HIPCC__) && !defined(CAVE_SIMT_EMUL)
 // k_tsp_hk_wide.hip: the list kernel, then grid workgroups of kTspHkWideThreads threads, tsp_hk_wide_lds_bytes(P.n) bytes of LDS
-hipError_t launch_tsp_hk_wide(unsigned grid, hipStream_t stream, const TspHkWideParams& P);
+hipError_t launch_tsp_hk_wide(unsigned grid, hipStream_t stream, const TspHkParams& P);
 #endif
 
 }  // namespace cave

@@ -102,6 +102,24 @@ CAVE_HOSTDEV uint32_t vrp_dp_lds_bytes(int64_t n, int64_t K) {
   return vrp_dp_lds_layout(n).tab + (uint32_t)((t == 0 ? tsp_hk_table_bytes(n) : 0) + (t <= 1 ? vrp_dp_part_bytes(n, K) : 0));
 }
 
+
+// cave_hip_vrp_dp_solve: its checks, its grid and its parameter block (solver_entry.h)
+inline int32_t vrp_dp_plan(const float* costs, const float* eval_costs, const float* demands, double capacity, int64_t K, int64_t N,
+                           int64_t n, float* sol, double* obj, double* eval, int32_t* routes, int32_t* status, void* workspace,
+                           int64_t workspace_bytes, VrpDpParams* P, int64_t* grid, char* msg) {
+  const bool valid = vrp_dp_valid(n, K);
+  const int64_t slot = valid ? vrp_dp_slot_bytes(n, K) : 0;
+  const int32_t rc = solver_plan(
+      "vrp_dp_solve", valid ? nullptr : "need 3 <= n <= 14 and 1 <= K <= 8", eval && !eval_costs, N,
+      capacity > 0.0 && capacity <= 1.7976931348623157e308 ? nullptr : "capacity must be finite and positive", 0, slot,
+      "this (n, K) needs an 8-byte aligned workspace of at least one slot (cave_hip_vrp_dp_slot_bytes)", workspace, workspace_bytes,
+      costs && demands ? nullptr : "costs or demands is null", kTspHkLdsGrid, grid, msg);
+  if (rc != CAVE_OK || *grid == 0) return rc;
+  tsp_hk_fill(P, costs, eval_costs, N, n, sol, obj, eval, status, workspace, 0, slot);
+  P->demands = demands; P->capacity = capacity; P->K = (int32_t)K; P->routes = routes;
+  return CAVE_OK;
+}
+
 #if defined(CAVE_GPU_CODE)
 // The lexicographic minimum of the threads' (v, idx) pairs: afterwards redv[0], redi[0] (every thread may read them until
 // the next call).  nt is a power of two.  Called by the whole workgroup.

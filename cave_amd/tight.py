@@ -111,39 +111,81 @@ def sp_gen_data(num_data: int, num_feat: int, h: int, w: int, deg: int = 4, nois
     return x.astype(np.float32), c.astype(np.float32)
 
 
-def _sp_grid_call(costs, h: int, w: int, eval_costs=None, cones: bool = False):
-    """One launch of cave_hip_sp_grid_solve on a (N, d) float32 device tensor -> (sols, objs, evals or None, key, val)."""
+def _hip_solve(who: str, entry: str, costs, eval_costs, d: int, columns: str, own, ws_args, call):
+    """One launch of the exact-solver entry cave_hip_<entry>_solve, the part `sp_solve_hip`, `tsp_solve_hip[_wide]` and
+    `vrp_solve_hip` share: costs (N, d) float32 on the device and eval_costs like it or None are checked (`who` and
+    `columns`, e.g. "a TSP on 5 nodes has 10 edges", go into the messages); sols, objs, evals (with eval_costs) and the
+    status are allocated, then the entry's own tensors `own(N, device)` (a list) and -- `ws_args`: the size query's
+    arguments in front of N, None: the entry has no workspace -- the default workspace for the call;
+    `call(solve, costs, eval_costs, N, sols, objs, evals, status, own, ws, ws_bytes, stream)`, all pointers, launches
+    under the device guard.  -> (sols, objs, evals or None, index of the first instance whose status is not OK or None,
+    status, own)."""
     import torch
 
     from . import _lib
 
     lib = _lib.load()
-    h, w = int(h), int(w)
-    d = h * (w - 1) + (h - 1) * w
     if not (isinstance(costs, torch.Tensor) and costs.is_cuda and costs.dtype == torch.float32 and costs.dim() == 2):
-        raise ValueError("sp_solve_hip: costs must be a (N, d) float32 tensor on the device")
+        raise ValueError(f"{who}: costs must be a (N, d) float32 tensor on the device")
     if costs.shape[1] != d:
-        raise ValueError(f"sp_solve_hip: a {h} x {w} grid has {d} arcs, costs has {costs.shape[1]} columns")
+        raise ValueError(f"{who}: {columns}, costs has {costs.shape[1]} columns")
     costs = costs.contiguous()
     if eval_costs is not None:
         if not (isinstance(eval_costs, torch.Tensor) and eval_costs.dtype == torch.float32 and eval_costs.shape == costs.shape
                 and eval_costs.device == costs.device):
-            raise ValueError("sp_solve_hip: eval_costs must match costs in shape, dtype and device")
+            raise ValueError(f"{who}: eval_costs must match costs in shape, dtype and device")
         eval_costs = eval_costs.contiguous()
     N, dev = costs.shape[0], costs.device
     sols = torch.empty(N, d, dtype=torch.float32, device=dev)
     objs = torch.empty(N, dtype=torch.float64, device=dev)
     evals = torch.empty(N, dtype=torch.float64, device=dev) if eval_costs is not None else None
     status = torch.empty(N, dtype=torch.int32, device=dev)
-    key = torch.empty(N * 5 * d, dtype=torch.int32, device=dev) if cones else None
-    val = torch.empty(N * 5 * d, dtype=torch.float32, device=dev) if cones else None
+    own = own(N, dev)
+    ws_bytes = 0
+    if ws_args is not None:
+        ws_bytes = int(getattr(lib, f"cave_hip_{entry}_workspace_bytes")(*ws_args, N))
+        if ws_bytes < 0:
+            _lib.check(ws_bytes, f"cave_hip_{entry}_workspace_bytes")
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev) if ws_bytes and N else None
+    p = _lib.ptr
     with torch.cuda.device(dev):
-        _lib.check(lib.cave_hip_sp_grid_solve(_lib.ptr(costs), _lib.ptr(eval_costs), N, h, w, _lib.ptr(sols), _lib.ptr(objs),
-                                              _lib.ptr(evals), _lib.ptr(status), _lib.ptr(key), _lib.ptr(val),
-                                              _lib.current_stream()), "cave_hip_sp_grid_solve")
-    if N and bool((status != _lib.ST_OK).any()):
-        b = int(torch.nonzero(status != _lib.ST_OK)[0])
-        raise ValueError(f"sp_solve_hip: instance {b} has a non-finite cost")
+        _lib.check(call(getattr(lib, f"cave_hip_{entry}_solve"), p(costs), p(eval_costs), N, p(sols), p(objs), p(evals), p(status),
+                        [p(t) for t in own], p(ws), ws_bytes if ws is not None else 0, _lib.current_stream()),
+                   f"cave_hip_{entry}_solve")
+    bad = int(torch.nonzero(status != _lib.ST_OK)[0]) if N and bool((status != _lib.ST_OK).any()) else None
+    return sols, objs, evals, bad, status, own
+
+
+def _regret_hip(evals_of, pred_costs, true_costs, true_objs, device) -> float:
+    """The `device=` branch of `sp_regret`, `tsp_regret` and `vrp_regret`: the three inputs go to the device as float32,
+    `evals_of(pred, true)` solves under pred and prices under true there, the fp64 sums are formed there."""
+    import torch
+
+    device = torch.device(device)
+    cp, c, z = (torch.as_tensor(t).detach().to(device=device, dtype=torch.float32) for t in (pred_costs, true_costs, true_objs))
+    evals = evals_of(cp, c)
+    z = z.reshape(-1).to(torch.float64)
+    return float(((evals - z).sum() / (z.abs().sum() + 1e-7)).item())
+
+
+def _sp_grid_call(costs, h: int, w: int, eval_costs=None, cones: bool = False):
+    """One launch of cave_hip_sp_grid_solve on a (N, d) float32 device tensor -> (sols, objs, evals or None, key, val)."""
+    import torch
+
+    from . import _lib
+
+    _lib.load()  # (no device: ImportError before any check of the arguments)
+    h, w = int(h), int(w)
+    d = h * (w - 1) + (h - 1) * w
+
+    def own(N, dev):
+        return [torch.empty(N * 5 * d, dtype=t, device=dev) if cones else None for t in (torch.int32, torch.float32)]
+
+    sols, objs, evals, bad, _, (key, val) = _hip_solve(
+        "sp_solve_hip", "sp_grid", costs, eval_costs, d, f"a {h} x {w} grid has {d} arcs", own, None,
+        lambda solve, c, e, N, s, o, ev, st, x, ws, wsb, stream: solve(c, e, N, h, w, s, o, ev, st, x[0], x[1], stream))
+    if bad is not None:
+        raise ValueError(f"sp_solve_hip: instance {bad} has a non-finite cost")
     return sols, objs, evals, key, val
 
 
@@ -220,13 +262,7 @@ def sp_regret(pred_costs: np.ndarray, true_costs: np.ndarray, true_objs: np.ndar
     With `device`: arrays or tensors, moved to the device if they are not there; solved and priced there in one launch
     (fp64 sums), only the scalar comes back."""
     if device is not None:
-        import torch
-
-        device = torch.device(device)
-        cp, c, z = (torch.as_tensor(t).detach().to(device=device, dtype=torch.float32) for t in (pred_costs, true_costs, true_objs))
-        _, _, evals = sp_solve_hip(cp, h, w, eval_costs=c)
-        z = z.reshape(-1).to(torch.float64)
-        return float(((evals - z).sum() / (z.abs().sum() + 1e-7)).item())
+        return _regret_hip(lambda cp, c: sp_solve_hip(cp, h, w, eval_costs=c)[2], pred_costs, true_costs, true_objs, device)
     loss = 0.0
     for cp, c, z in zip(pred_costs, true_costs, true_objs):
         s, _ = sp_solve(cp, h, w)
@@ -435,45 +471,22 @@ class TSPConeDataset:
 
 
 def _tsp_hk_hip(who: str, entry: str, lo: int, hi: int, costs, n: int, eval_costs):
-    """`tsp_solve_hip` and `tsp_solve_hip_wide`: the checks, the outputs, the default workspace of the C ABI entry
-    cave_hip_<entry>_solve (allocated for the call) and the launch."""
+    """`tsp_solve_hip` and `tsp_solve_hip_wide`: the node range, the tours and the launch of cave_hip_<entry>_solve."""
     import torch
 
     from . import _lib
 
-    lib = _lib.load()
+    _lib.load()  # (no device: ImportError before any check of the arguments)
     n = int(n)
     if not lo <= n <= hi:
         raise ValueError(f"{who}: Held-Karp on the device takes {lo} <= n <= {hi} nodes, not {n}")
     d = n * (n - 1) // 2
-    if not (isinstance(costs, torch.Tensor) and costs.is_cuda and costs.dtype == torch.float32 and costs.dim() == 2):
-        raise ValueError(f"{who}: costs must be a (N, d) float32 tensor on the device")
-    if costs.shape[1] != d:
-        raise ValueError(f"{who}: a TSP on {n} nodes has {d} edges, costs has {costs.shape[1]} columns")
-    costs = costs.contiguous()
-    if eval_costs is not None:
-        if not (isinstance(eval_costs, torch.Tensor) and eval_costs.dtype == torch.float32 and eval_costs.shape == costs.shape
-                and eval_costs.device == costs.device):
-            raise ValueError(f"{who}: eval_costs must match costs in shape, dtype and device")
-        eval_costs = eval_costs.contiguous()
-    N, dev = costs.shape[0], costs.device
-    sols = torch.empty(N, d, dtype=torch.float32, device=dev)
-    objs = torch.empty(N, dtype=torch.float64, device=dev)
-    tours = torch.empty(N, n, dtype=torch.int32, device=dev)
-    evals = torch.empty(N, dtype=torch.float64, device=dev) if eval_costs is not None else None
-    status = torch.empty(N, dtype=torch.int32, device=dev)
-    ws_bytes = int(getattr(lib, f"cave_hip_{entry}_workspace_bytes")(n, N))
-    if ws_bytes < 0:
-        _lib.check(ws_bytes, f"cave_hip_{entry}_workspace_bytes")
-    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev) if ws_bytes and N else None
-    with torch.cuda.device(dev):
-        _lib.check(getattr(lib, f"cave_hip_{entry}_solve")(_lib.ptr(costs), _lib.ptr(eval_costs), N, n, _lib.ptr(sols), _lib.ptr(objs),
-                                                           _lib.ptr(evals), _lib.ptr(tours), _lib.ptr(status), _lib.ptr(ws),
-                                                           ws_bytes if ws is not None else 0, _lib.current_stream()),
-                   f"cave_hip_{entry}_solve")
-    if N and bool((status != _lib.ST_OK).any()):
-        b = int(torch.nonzero(status != _lib.ST_OK)[0])
-        raise ValueError(f"{who}: instance {b} has a non-finite cost")
+    sols, objs, evals, bad, _, (tours,) = _hip_solve(
+        who, entry, costs, eval_costs, d, f"a TSP on {n} nodes has {d} edges",
+        lambda N, dev: [torch.empty(N, n, dtype=torch.int32, device=dev)], (n,),
+        lambda solve, c, e, N, s, o, ev, st, x, ws, wsb, stream: solve(c, e, N, n, s, o, ev, x[0], st, ws, wsb, stream))
+    if bad is not None:
+        raise ValueError(f"{who}: instance {bad} has a non-finite cost")
     return (sols, objs, tours) if eval_costs is None else (sols, objs, tours, evals)
 
 
@@ -502,13 +515,8 @@ def tsp_regret(pred_costs: np.ndarray, true_costs: np.ndarray, true_objs: np.nda
     (fp64 sums), only the scalar comes back.  Up to 14 nodes through `tsp_solve_hip`, 15 to 20 through
     `tsp_solve_hip_wide`; without a device the host solver's limit of 14 nodes holds."""
     if device is not None:
-        import torch
-
-        device = torch.device(device)
-        cp, c, z = (torch.as_tensor(t).detach().to(device=device, dtype=torch.float32) for t in (pred_costs, true_costs, true_objs))
-        evals = (tsp_solve_hip if int(n) <= 14 else tsp_solve_hip_wide)(cp, n, eval_costs=c)[3]
-        z = z.reshape(-1).to(torch.float64)
-        return float(((evals - z).sum() / (z.abs().sum() + 1e-7)).item())
+        solve = tsp_solve_hip if int(n) <= 14 else tsp_solve_hip_wide
+        return _regret_hip(lambda cp, c: solve(cp, n, eval_costs=c)[3], pred_costs, true_costs, true_objs, device)
     loss = 0.0
     for cp, c, z in zip(pred_costs, true_costs, true_objs):
         s, _, _ = tsp_solve(cp, n)
@@ -715,7 +723,7 @@ def vrp_solve_hip(costs, n: int, demands, capacity: float, num_vehicle: int, eva
 
     from . import _lib
 
-    lib = _lib.load()
+    _lib.load()  # (no device: ImportError before any check of the arguments)
     n, K = int(n), int(num_vehicle)
     if not 3 <= n <= 14:
         raise ValueError(f"vrp_solve_hip: the dynamic program on the device takes 3 <= n <= 14 nodes, not {n}")
@@ -725,40 +733,21 @@ def vrp_solve_hip(costs, n: int, demands, capacity: float, num_vehicle: int, eva
     if not (np.isfinite(capacity) and capacity > 0):
         raise ValueError("vrp_solve_hip: capacity must be finite and positive")
     d = n * (n - 1) // 2
-    if not (isinstance(costs, torch.Tensor) and costs.is_cuda and costs.dtype == torch.float32 and costs.dim() == 2):
-        raise ValueError("vrp_solve_hip: costs must be a (N, d) float32 tensor on the device")
-    if costs.shape[1] != d:
-        raise ValueError(f"vrp_solve_hip: a CVRP on {n} nodes has {d} edges, costs has {costs.shape[1]} columns")
-    costs = costs.contiguous()
-    if eval_costs is not None:
-        if not (isinstance(eval_costs, torch.Tensor) and eval_costs.dtype == torch.float32 and eval_costs.shape == costs.shape
-                and eval_costs.device == costs.device):
-            raise ValueError("vrp_solve_hip: eval_costs must match costs in shape, dtype and device")
-        eval_costs = eval_costs.contiguous()
-    N, dev = costs.shape[0], costs.device
-    if not isinstance(demands, torch.Tensor):
-        demands = torch.from_numpy(np.array(demands, dtype=np.float32))
-    q = demands.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
-    if q.numel() != n - 1:
-        raise ValueError(f"vrp_solve_hip: {n - 1} customers, {q.numel()} demands")
-    sols = torch.empty(N, d, dtype=torch.float32, device=dev)
-    objs = torch.empty(N, dtype=torch.float64, device=dev)
-    routes = torch.empty(N, n + K, dtype=torch.int32, device=dev)
-    evals = torch.empty(N, dtype=torch.float64, device=dev) if eval_costs is not None else None
-    status = torch.empty(N, dtype=torch.int32, device=dev)
-    ws_bytes = int(lib.cave_hip_vrp_dp_workspace_bytes(n, K, N))
-    if ws_bytes < 0:
-        _lib.check(ws_bytes, "cave_hip_vrp_dp_workspace_bytes")
-    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev) if ws_bytes else None
-    with torch.cuda.device(dev):
-        _lib.check(lib.cave_hip_vrp_dp_solve(_lib.ptr(costs), _lib.ptr(eval_costs), _lib.ptr(q), capacity, K, N, n, _lib.ptr(sols),
-                                             _lib.ptr(objs), _lib.ptr(evals), _lib.ptr(routes), _lib.ptr(status), _lib.ptr(ws),
-                                             ws_bytes, _lib.current_stream()), "cave_hip_vrp_dp_solve")
-    if N and bool((status != _lib.ST_OK).any()):
-        b = int(torch.nonzero(status != _lib.ST_OK)[0])
-        if int(status[b]) == _lib.ST_INFEASIBLE:
-            raise ValueError(f"vrp_solve_hip: instance {b} is infeasible (no partition into feasible routes)")
-        raise ValueError(f"vrp_solve_hip: instance {b} has a non-finite cost, or a demand is negative or non-finite")
+
+    def own(N, dev):  # the routes, and the demands on the device
+        q = demands if isinstance(demands, torch.Tensor) else torch.from_numpy(np.array(demands, dtype=np.float32))
+        q = q.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        if q.numel() != n - 1:
+            raise ValueError(f"vrp_solve_hip: {n - 1} customers, {q.numel()} demands")
+        return [torch.empty(N, n + K, dtype=torch.int32, device=dev), q]
+
+    sols, objs, evals, bad, status, (routes, _) = _hip_solve(
+        "vrp_solve_hip", "vrp_dp", costs, eval_costs, d, f"a CVRP on {n} nodes has {d} edges", own, (n, K),
+        lambda solve, c, e, N, s, o, ev, st, x, ws, wsb, stream: solve(c, e, x[1], capacity, K, N, n, s, o, ev, x[0], st, ws, wsb, stream))
+    if bad is not None:
+        if int(status[bad]) == _lib.ST_INFEASIBLE:
+            raise ValueError(f"vrp_solve_hip: instance {bad} is infeasible (no partition into feasible routes)")
+        raise ValueError(f"vrp_solve_hip: instance {bad} has a non-finite cost, or a demand is negative or non-finite")
     return (sols, objs, routes) if eval_costs is None else (sols, objs, routes, evals)
 
 
@@ -812,13 +801,8 @@ def vrp_regret(pred_costs: np.ndarray, true_costs: np.ndarray, true_objs: np.nda
     (fp64 sums), only the scalar comes back."""
     demands = np.asarray(demands.detach().cpu() if hasattr(demands, "detach") else demands, dtype=np.float32).reshape(-1)
     if device is not None:
-        import torch
-
-        device = torch.device(device)
-        cp, c, z = (torch.as_tensor(t).detach().to(device=device, dtype=torch.float32) for t in (pred_costs, true_costs, true_objs))
-        evals = vrp_solve_hip(cp, n, demands, capacity, num_vehicle, eval_costs=c)[3]
-        z = z.reshape(-1).to(torch.float64)
-        return float(((evals - z).sum() / (z.abs().sum() + 1e-7)).item())
+        return _regret_hip(lambda cp, c: vrp_solve_hip(cp, n, demands, capacity, num_vehicle, eval_costs=c)[3], pred_costs, true_costs,
+                           true_objs, device)
     loss = 0.0
     for cp, c, z in zip(pred_costs, true_costs, true_objs):
         s, _, _ = vrp_solve(cp, n, demands, capacity, num_vehicle)
