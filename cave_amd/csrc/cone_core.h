@@ -200,7 +200,11 @@ CAVE_HD int32_t build_cone(C& c, Arena& ar, ConeBuild& cb) {
     uint32_t r = cb.vraw[i];
     uint32_t lo = cb.rptr[r], hi = cb.rptr[r + 1];
     // signature of the row and of its negation: length + the first kHashPrefix entries (two 32-bit
-    // FNV-1a streams each).  Candidates are verified entry by entry below, so a prefix is enough.
+    // FNV-1a streams each).  Candidates are verified entry by entry below, so a collision never pairs rows that are
+    // not exact negations -- but it costs pairs: different rows of one length that agree in their first kHashPrefix
+    // entries share a signature, none of them is then the only match, and each stays unpaired even with its exact
+    // twin present (a, b, -a, -b: p = 4 bound rows instead of 2 free ones; same cone, same projection, twice the
+    // rows, a singular Newton system, bound rows spent against the lite form's limit of 8).  DESIGN.md 4a.
     uint32_t a0 = 0x811c9dc5u ^ (hi - lo), a1 = 0x9747b28cu + (hi - lo), b0 = a0, b1 = a1;
     const uint32_t hend = (hi - lo < kHashPrefix) ? hi : lo + kHashPrefix;
     for (uint32_t e = lo; e < hend; ++e) {

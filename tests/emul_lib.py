@@ -316,6 +316,36 @@ class Simt:
         assert rc == 0, rc
         return out
 
+    def pack(self, ctrs, nnz_cap=0, lds_bytes=0, waves=1, seed=0):
+        """run_pack_instance on the real workgroup shapes (cave_simt_pack_fill: WaveCtx, BlockCtx<2>, BlockCtx<4>, the
+        wide four-wave shape for waves = 8): count pass, then the fill into an exact-fit store of host arrays, as
+        Emul.pack does on the serial context -> (store, arrays, status of the count pass, status of the fill pass).
+        The multi-thread forms of build_cone -- the team-shared signature scan, the compactions, one wave per long
+        row, the atomic CSC fill and its sort -- write this store."""
+        ctrs = np.ascontiguousarray(ctrs, dtype=np.float32)
+        B, m, d = ctrs.shape
+        n_rows = np.zeros(B, np.int32); n_nnz = np.zeros(B, np.int32)
+        st1 = np.full(B, -7, np.int32); st2 = np.full(B, -7, np.int32)
+        head = (_p(ctrs), C.c_int64(B), C.c_int64(m), C.c_int64(d), C.c_int32(nnz_cap), C.c_int32(lds_bytes),
+                C.c_int32(waves), C.c_uint64(seed))
+        rc = self.lib.cave_simt_pack_fill(*head, None, C.c_int64(0), _p(n_rows), _p(n_nnz), _p(st1))
+        assert rc == 0, rc
+        row_off = np.concatenate([[0], np.cumsum(n_rows, dtype=np.int64)]).astype(np.int64)
+        nnz_off = np.concatenate([[0], np.cumsum(n_nnz, dtype=np.int64)]).astype(np.int64)
+        R, Z = int(row_off[-1]), int(nnz_off[-1])
+        arrs = {
+            "row_off": row_off, "nnz_off": nnz_off, "n_valid": np.zeros(B, np.int32), "flags": np.zeros(B, np.uint8),
+            "usign": np.zeros(B * d, np.uint8), "avg": np.zeros(B * d, np.float32),
+            "vkind": np.zeros(max(R, 1), np.uint8), "rlo": np.zeros(max(R, 1), np.uint32),
+            "rhi": np.zeros(max(R, 1), np.uint32), "ccol": np.zeros(max(Z, 1), np.uint16),
+            "cval": np.zeros(max(Z, 1), np.float32), "cptr": np.zeros(B * (d + 1), np.uint32),
+            "cvar": np.zeros(max(Z, 1), np.uint16), "cvalc": np.zeros(max(Z, 1), np.float32),
+        }
+        st = Store(n=B, d=d, reserved=0, **{k: v.ctypes.data for k, v in arrs.items()})
+        rc = self.lib.cave_simt_pack_fill(*head, C.byref(st), C.c_int64(0), None, None, _p(st2))
+        assert rc == 0, rc
+        return st, arrs, st1, st2
+
     def cone_packed(self, store, arrs, max_rows, max_nnz, ids, pred, mode, sign=-1.0, inner_ratio=0.2, max_iter=0,
                     waves=1, seed=0, diet=False):
         """diet: launch with the LDS figure of the diet layout (cave_hip_packed_lds_bytes mode 3): instances whose
