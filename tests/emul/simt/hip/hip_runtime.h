@@ -356,7 +356,14 @@ template <class P, class T> static inline T __hip_atomic_fetch_add(P p, T v, int
 #define __builtin_amdgcn_mbcnt_lo(m, b) ::simt::mbcnt_lo((uint32_t)(m), (uint32_t)(b))
 #define __builtin_amdgcn_mbcnt_hi(m, b) ::simt::mbcnt_hi((uint32_t)(m), (uint32_t)(b))
 #ifdef SIMT_APPROX_RCP
-#define __builtin_amdgcn_rcp(x) ((double)(1.0f / (float)(x)))  /* ~24 bits, like v_rcp_f64 before its Newton steps */
+/* ~24 bits, like v_rcp_f64 before its Newton steps -- of the MANTISSA: the exponent keeps the range of a double (the
+   instruction returns 1e300 for the 1e-300 a dropped pivot is clamped to; a float would turn that into 1 / 0) */
+static inline double simt_rcp24(double x) {
+  int e = 0;
+  const double m = frexp(x, &e);
+  return ldexp((double)(1.0f / (float)m), -e);
+}
+#define __builtin_amdgcn_rcp(x) simt_rcp24((double)(x))
 #else
 #define __builtin_amdgcn_rcp(x) (1.0 / (x))
 #endif

@@ -262,7 +262,8 @@ def warm_cache(n):
 # compiled by g++ against a shim <hip/hip_runtime.h> in which every lane is a fiber.  TEST INFRASTRUCTURE ONLY.
 _SIMT_SRC = os.path.join(_HERE, "emul", "simt_abi.cpp")
 _SIMT_DEPS = _DEPS + [_SIMT_SRC, os.path.join(_HERE, "emul", "simt", "hip", "hip_runtime.h"),
-                      os.path.join(_HERE, "prims", "prim_entries.h"), os.path.join(_HERE, "prims", "op_entries.h")] + [
+                      os.path.join(_HERE, "prims", "prim_entries.h"), os.path.join(_HERE, "prims", "model_entries.h"),
+                      os.path.join(_HERE, "prims", "op_entries.h")] + [
     os.path.join(_HERE, "..", "cave_amd", "csrc", n) for n in ("wave_prims.h", "ctx_wave.h", "ctx_block.h", "cone_step.h")]
 
 
@@ -399,6 +400,10 @@ class Simt:
         """one solver alone on a batch of systems (prim_run_host)"""
         return prim_run_host(self.lib, kind, H, rhs, **kw)
 
+    def model_run(self, kind, H, theta, g, nF, **kw):
+        """one model minimisation alone on a batch (model_run_host)"""
+        return model_run_host(self.lib, kind, H, theta, g, nF, **kw)
+
     # ---- the fused step kernel (cone_step.h): pack half, solve half (cold / warm), lite_from_packed
     def step_lds_bytes(self, m_max, d):
         """cave_hip_step_lds_bytes of the product (the same step_limits): < 0 = the shape has no such launch."""
@@ -470,6 +475,9 @@ class PrimBatch(C.Structure):
         ("reg_rel", C.c_double), ("H", C.c_void_p), ("h_stride", C.c_int64), ("rhs", C.c_void_p), ("act", C.c_void_p),
         ("ex", C.c_void_p), ("x", C.c_void_p), ("M", C.c_void_p), ("m_stride", C.c_int64), ("aux", C.c_void_p),
         ("ws", C.c_void_p), ("ws_stride", C.c_int64), ("fail", C.c_void_p),
+        # the model minimisation alone (tests/prims/model_entries.h); NULL for the other entries
+        ("theta", C.c_void_p), ("g", C.c_void_p), ("ord", C.c_void_p), ("tc", C.c_void_p), ("moved", C.c_void_p),
+        ("sact_out", C.c_void_p), ("ss_out", C.c_void_p),
     ]
 
 
@@ -477,6 +485,7 @@ PRIM_KINDS = {  # enum of prim_entries.h
     "gj": 0, "gj_lower": 1, "gjs": 2, "gjs_tri": 3, "spd_b2": 4, "spd_b4": 5, "spd_l2": 6, "spd_l4": 7, "spd_solo": 8,
     "tri_l4": 9, "tri_b4": 10, "tri_b2": 11, "partial": 12, "tableau": 13, "dense_w2": 14, "dense_w4": 15,
     "bandw1": 16, "bandw2": 17, "band_hot_w1": 18, "band_hot_l2": 19, "band_hot_l4": 20, "band_cold_l4": 21,
+    "lite_model": 22, "dense_model_w1": 23, "dense_model_w2": 24, "dense_model_w4": 25,
 }
 
 
@@ -486,6 +495,10 @@ def prim_m_entries(kind, p, nF):
         return max(1, p * (p - nF))
     if kind == "tableau":
         return 72
+    if kind == "lite_model":
+        return p * (p | 1)
+    if kind.startswith("dense_model"):
+        return 1
     if kind.startswith("dense"):
         return ((p + 1) // 2) * (p + 1)
     return 1
@@ -517,6 +530,44 @@ def prim_run_host(lib, kind, H, rhs, act=None, reg_rel=0.0, nF=0, bw=0, ex=(), x
                   fail=out["fail"].ctypes.data)
     rc = lib.cave_simt_prim_run(C.c_int32(k), C.byref(a), C.c_uint64(seed))
     assert rc == 0, (rc, kind, p, nF, bw)
+    return out
+
+
+POISON_BITS = 0x7FF8000000ABCDEF  # poison_f64 of tests/prims/prim_entries.h
+
+
+def model_buffers(kind, H, theta, g, ord_, nF):
+    """the arrays of one launch of a model-step entry: inputs as contiguous numpy arrays, outputs preset (tc poisoned,
+    moved = -7, sact_out = 0xee, ss_out and M poisoned) -> (inputs, outputs, m)"""
+    theta = np.ascontiguousarray(theta, np.float64)
+    B, p = theta.shape
+    g = np.ascontiguousarray(g, np.float64)
+    H = np.ascontiguousarray(H, np.float64).reshape(B, -1)
+    ord_ = np.ascontiguousarray(np.tile(np.arange(p, dtype=np.uint16), (B, 1)) if ord_ is None else ord_, np.uint16)
+    assert g.shape == (B, p) and ord_.shape == (B, p) and (np.sort(ord_, axis=1) == np.arange(p)).all()
+    m, nI = prim_m_entries(kind, p, nF), p - nF
+    poison = np.array([POISON_BITS], np.uint64).view(np.float64)[0]
+    out = {"tc": np.full((B, p), poison), "moved": np.full(B, -7, np.int32), "sact": np.full((B, max(nI, 1)), 0xEE, np.uint8),
+           "ss": np.full((B, max(nI, 1)), poison), "M": np.full((B, m), poison)}
+    return {"H": H, "theta": theta, "g": g, "ord": ord_}, out, m
+
+
+def model_run_host(lib, kind, H, theta, g, nF, reg_rel=0.0, ord_=None, seed=0):
+    """One batch through a model-step entry of cave_simt_prim_run on host arrays.  H [B, h]: full rows (lite_model) or
+    the folded triangle in elimination order (dense_model_*); theta, g [B, p] in reduced-row order; ord_ [B, p] uint16
+    -> dict(tc [B, p], moved [B], sact [B, nI], ss [B, nI], M [B, m])."""
+    k = PRIM_KINDS[kind]
+    ins, out, m = model_buffers(kind, H, theta, g, ord_, nF)
+    B, p = ins["theta"].shape
+    lib.cave_simt_prim_info.restype = C.c_int64
+    hs = int(lib.cave_simt_prim_info(C.c_int32(k), C.c_int32(0), C.c_int32(p), C.c_int32(nF), C.c_int32(0)))
+    assert hs >= 0 and ins["H"].shape[1] == hs, (kind, p, nF, ins["H"].shape, hs)
+    a = PrimBatch(B=B, p=p, nF=nF, bw=0, n_ex=0, reg_rel=reg_rel, H=ins["H"].ctypes.data, h_stride=hs, M=out["M"].ctypes.data,
+                  m_stride=m, theta=ins["theta"].ctypes.data, g=ins["g"].ctypes.data, ord=ins["ord"].ctypes.data,
+                  tc=out["tc"].ctypes.data, moved=out["moved"].ctypes.data, sact_out=out["sact"].ctypes.data,
+                  ss_out=out["ss"].ctypes.data)
+    rc = lib.cave_simt_prim_run(C.c_int32(k), C.byref(a), C.c_uint64(seed))
+    assert rc == 0, (rc, kind, p, nF)
     return out
 
 

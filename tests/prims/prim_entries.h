@@ -7,8 +7,11 @@
 // algorithm code: the solvers are the ones of cave_amd/csrc, untouched.  Never loaded by cave_amd.
 //
 // Include after cone_core.h / ctx_wave.h / ctx_block.h (cone_band.h and cone_dense.h come with cone_core.h).
+// The model minimisation alone (lite_model_step / dense_model_step) is in model_entries.h, included below.
 #pragma once
 #include <stdint.h>
+
+#include "../../cave_amd/csrc/cone_step.h"  // lite_scratch_doubles: what the product reserves for lite_model_step
 
 namespace cave_prims {
 using namespace cave;
@@ -29,6 +32,14 @@ struct PrimBatch {
   double* ws;            // [B, ws_stride]  global workspace (band: factor rows; cold band form: every work array)
   int64_t ws_stride;
   int32_t* fail;         // [B]  band wave form: the hand-over failure word; tableau: mask of refused exchanges
+  // the model minimisation alone (model_entries.h); H: full rows (lite) / folded triangle in elimination order (dense)
+  const double* theta;   // [B, p]  multipliers, reduced-row order
+  const double* g;       // [B, p]  gradient, reduced-row order
+  const uint16_t* ord;   // [B, p]  dense: reduced row at elimination position q (free rows at q < nF)
+  double* tc;            // [B, p]  the trial point (poisoned by the caller)
+  int32_t* moved;        // [B]     what the function returned (preset to -7)
+  uint8_t* sact_out;     // [B, nI] dense: the held-at-zero flags the loop ended with
+  double* ss_out;        // [B, nI] dense: the step of the last inner round (tc - ss: the working point it started from)
 };
 
 enum : int32_t {
@@ -54,7 +65,11 @@ enum : int32_t {
   K_BAND_HOT_L2 = 19,   // solve_spd_band<BlockCtx<2, true>, true>
   K_BAND_HOT_L4 = 20,   // solve_spd_band<BlockCtx<4, true>, true>
   K_BAND_COLD_L4 = 21,  // solve_spd_band<BlockCtx<4, true>, false>: every work array in the global workspace
-  K_COUNT = 22,
+  K_LITE_MODEL = 22,      // lite_model_step on SoloCtx<32, 4>             H = full rows [p, p] -> M = H as left in LDS [p, p | 1]
+  K_DENSE_MODEL_W1 = 23,  // dense_model_step on WaveCtx (cone_packed_large_kernel<Ctx1, 2>)
+  K_DENSE_MODEL_W2 = 24,  //                  on BlockCtx<2, true>
+  K_DENSE_MODEL_W4 = 25,  //                  on BlockCtx<4, true>
+  K_COUNT = 26,
 };
 
 using SoloT = SoloCtx<32, 4>;
@@ -73,6 +88,9 @@ template <> struct PrimCtx<K_BANDW2> { using type = BlockCtx<2, true>; };
 template <> struct PrimCtx<K_BAND_HOT_L2> { using type = BlockCtx<2, true>; };
 template <> struct PrimCtx<K_BAND_HOT_L4> { using type = BlockCtx<4, true>; };
 template <> struct PrimCtx<K_BAND_COLD_L4> { using type = BlockCtx<4, true>; };
+template <> struct PrimCtx<K_LITE_MODEL> { using type = SoloT; };
+template <> struct PrimCtx<K_DENSE_MODEL_W2> { using type = BlockCtx<2, true>; };
+template <> struct PrimCtx<K_DENSE_MODEL_W4> { using type = BlockCtx<4, true>; };
 
 template <class C> struct CtxInfo { static constexpr uint32_t scratch = C::SCRATCH_BYTES; static constexpr int min_waves = C::MIN_WAVES_PER_EU; };
 template <> struct CtxInfo<SoloT> { static constexpr uint32_t scratch = 0; static constexpr int min_waves = 2; };
@@ -80,11 +98,24 @@ template <> struct CtxInfo<SoloT> { static constexpr uint32_t scratch = 0; stati
 constexpr bool kind_is_tri(int k) { return k == K_GJS_TRI || k == K_TRI_L4 || k == K_TRI_B4 || k == K_TRI_B2; }
 constexpr bool kind_is_reg(int k) { return k <= K_TRI_B2; }
 constexpr bool kind_is_band_team(int k) { return k >= K_BAND_HOT_W1 && k <= K_BAND_COLD_L4; }
+constexpr bool kind_is_dense_model(int k) { return k >= K_DENSE_MODEL_W1 && k <= K_DENSE_MODEL_W4; }
 constexpr int kind_threads(int k) {
-  return (k == K_SPD_B4 || k == K_SPD_L4 || k == K_TRI_L4 || k == K_TRI_B4 || k == K_DENSE_W4 || k == K_BAND_HOT_L4 || k == K_BAND_COLD_L4) ? 256
-       : (k == K_SPD_B2 || k == K_SPD_L2 || k == K_TRI_B2 || k == K_DENSE_W2 || k == K_BANDW2 || k == K_BAND_HOT_L2) ? 128 : 64;
+  return (k == K_SPD_B4 || k == K_SPD_L4 || k == K_TRI_L4 || k == K_TRI_B4 || k == K_DENSE_W4 || k == K_BAND_HOT_L4 || k == K_BAND_COLD_L4 || k == K_DENSE_MODEL_W4) ? 256
+       : (k == K_SPD_B2 || k == K_SPD_L2 || k == K_TRI_B2 || k == K_DENSE_W2 || k == K_BANDW2 || k == K_BAND_HOT_L2 || k == K_DENSE_MODEL_W2) ? 128 : 64;
 }
+// doubles lite_model_step indexes in w.ls_scr: XS [p * nI] and the nI multipliers behind it (lite_scratch_doubles of
+// cone_step.h, what the product reserves, is never smaller)
+CAVE_HOSTDEV uint32_t lite_model_scratch(int p, int nI) { return (uint32_t)(p * nI + nI); }
+// bytes of the DenseWork arrays as model_entries.h lays them out (the order of cone_instance.h; A and scr on 16-byte
+// boundaries), and the gap in front of them that makes the block end where dense_lds_bytes(p, nI) ends
+CAVE_HOSTDEV uint64_t model_dense_used(int p, int nI) {
+  const uint64_t P = (uint64_t)p, I = (uint64_t)nI, head = 8ull * fold_entries(p) + 24ull * P;
+  return head + (head & 8u) + 8ull * dense_scratch_entries(p) + 8ull * I * (I | 1u) + 32ull * I + 4ull * P + I;
+}
+CAVE_HOSTDEV uint32_t model_dense_lead(int p, int nI) { return (uint32_t)((dense_lds_bytes(p, nI) - model_dense_used(p, nI)) & ~15ull); }
 CAVE_HOSTDEV int kind_pmax(int k) {
+  if (k == K_LITE_MODEL) return kLiteMaxRows;
+  if (kind_is_dense_model(k)) return kDenseMaxP;
   if (k == K_SPD_SOLO) return 8;
   if (k == K_SPD_B4 || k == K_TRI_B4 || k == K_PARTIAL) return 32;
   if (k == K_TABLEAU) return 8;
@@ -94,6 +125,8 @@ CAVE_HOSTDEV int kind_pmax(int k) {
 }
 CAVE_HOSTDEV uint32_t up16(uint64_t n) { return (uint32_t)((n + 15u) & ~15ull); }
 CAVE_HOSTDEV int64_t kind_h_entries(int k, int p, int bw) {
+  if (k == K_LITE_MODEL) return (int64_t)p * p;
+  if (kind_is_dense_model(k)) return fold_entries(p);
   if (k == K_TABLEAU) return 72;
   if (kind_is_tri(k)) return (int64_t)p * (p + 1) / 2;
   if (k == K_DENSE_W2 || k == K_DENSE_W4) return fold_entries(p);
@@ -107,7 +140,7 @@ CAVE_HOSTDEV int band_team_ch(int k, int ld) {
 }
 // global workspace doubles per system
 CAVE_HOSTDEV int64_t kind_ws_entries(int k, int p, int bw) {
-  if (k < K_BANDW1) return 0;
+  if (k < K_BANDW1 || k > K_BAND_COLD_L4) return 0;
   const int64_t ld = bw + 1;
   int64_t n = (int64_t)p * ld;  // factor rows
   if (k == K_BAND_COLD_L4) n += ld * ld + p + 2 * (int64_t)band_team_ch(k, (int)ld) * ld;
@@ -117,6 +150,9 @@ CAVE_HOSTDEV int64_t kind_ws_entries(int k, int p, int bw) {
 CAVE_HOSTDEV bool kind_valid(int k, int p, int nF, int bw, int n_ex) {
   if (k < 0 || k >= K_COUNT || p < 1 || p > kind_pmax(k)) return false;
   if (k == K_PARTIAL) return nF >= 0 && nF <= p;
+  if (k == K_LITE_MODEL) return nF >= 0 && nF <= p && p - nF <= 8 && lite_model_scratch(p, p - nF) <= lite_scratch_doubles(p, p - nF);
+  if (kind_is_dense_model(k))
+    return nF >= 0 && nF <= p && p - nF <= kDenseMaxBound && model_dense_used(p, p - nF) <= dense_lds_bytes(p, p - nF);
   if (k == K_TABLEAU) return p == 8 && n_ex >= 0;
   if (k == K_DENSE_W2 || k == K_DENSE_W4) return nF >= 0 && nF <= p && p - nF <= kDenseMaxBound;
   if (k == K_BANDW1 || k == K_BANDW2) return band_wave_fits(bw, p);
@@ -128,6 +164,8 @@ CAVE_HOSTDEV uint32_t kind_lds_bytes(int k, int p, int nF, int bw) {
   const uint64_t P = (uint64_t)p, h = (uint64_t)kind_h_entries(k, p, bw);
   uint64_t n = 256;
   if (kind_is_reg(k)) n += up16(8 * h) + 2 * up16(8 * P) + up16(P);
+  else if (k == K_LITE_MODEL) n += up16(8 * P * (P | 1u)) + 5 * up16(8 * P) + up16(8ull * lite_model_scratch(p, p - nF));
+  else if (kind_is_dense_model(k)) n += 3 * up16(8 * P) + model_dense_lead(p, p - nF) + model_dense_used(p, p - nF);
   else if (k == K_PARTIAL) n += up16(8 * h) + 2 * up16(8 * P) + up16(8 * P * (uint64_t)(p - nF) + 8);
   else if (k == K_TABLEAU) n += 0;
   else if (k == K_DENSE_W2 || k == K_DENSE_W4) n += up16(8 * h) + 3 * up16(8 * P) + up16(8ull * dense_scratch_entries(p));
@@ -159,6 +197,10 @@ struct Carve {  // hands out 16-byte aligned pieces of the workgroup's LDS behin
 };
 
 __device__ __forceinline__ double poison_f64() { return __hiloint2double(0x7ff80000, 0x00abcdef); }
+
+}  // namespace cave_prims
+#include "model_entries.h"
+namespace cave_prims {
 
 template <int KIND>
 __device__ __forceinline__ void prim_body(unsigned char* smem, const PrimBatch& a, int64_t b) {
@@ -243,6 +285,10 @@ __device__ __forceinline__ void prim_body(unsigned char* smem, const PrimBatch& 
     dense_backsub(c, dw, p, nF);
     __syncthreads();
     for (int i = tid; i < p; i += NT) a.x[b * p + i] = dw.x[i];
+  } else if constexpr (KIND == K_LITE_MODEL) {
+    model_lite_body<C>(smem, a, b);
+  } else if constexpr (kind_is_dense_model(KIND)) {
+    model_dense_body<C>(smem, a, b);
   } else if constexpr (KIND == K_BANDW1 || KIND == K_BANDW2) {
     constexpr int NW = KIND == K_BANDW1 ? 1 : 2;
     double* win = lds.get<double>(band_wave_region(bw, p));
@@ -283,6 +329,7 @@ __device__ __forceinline__ void prim_body(unsigned char* smem, const PrimBatch& 
 
 // X(kind) for every entry
 #define CAVE_PRIM_KINDS(X) \
-  X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20) X(21)
+  X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20) X(21) \
+  X(22) X(23) X(24) X(25)
 
 }  // namespace cave_prims

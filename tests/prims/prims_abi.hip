@@ -53,6 +53,9 @@ int32_t CAVE_PRIMS_SYM(cave_prims_run)(int32_t kind, const PrimBatch* a, void* s
 #ifdef CAVE_PRIMS_DENSE_ONLY
     case K_DENSE_W2: return prim_launch<K_DENSE_W2>(*a, (hipStream_t)stream);
     case K_DENSE_W4: return prim_launch<K_DENSE_W4>(*a, (hipStream_t)stream);
+    case K_DENSE_MODEL_W1: return prim_launch<K_DENSE_MODEL_W1>(*a, (hipStream_t)stream);
+    case K_DENSE_MODEL_W2: return prim_launch<K_DENSE_MODEL_W2>(*a, (hipStream_t)stream);
+    case K_DENSE_MODEL_W4: return prim_launch<K_DENSE_MODEL_W4>(*a, (hipStream_t)stream);
 #else
 #define CAVE_PRIM_CASE(K) case K: return prim_launch<K>(*a, (hipStream_t)stream);
     CAVE_PRIM_KINDS(CAVE_PRIM_CASE)

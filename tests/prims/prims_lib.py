@@ -32,7 +32,7 @@ def build(verbose: bool = False) -> str:
     from cave_amd import _lib
 
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    deps = [_SRC, os.path.join(_HERE, "prim_entries.h"), os.path.join(_HERE, "op_entries.h")] + [_unit_src(u) for u in _UNITS] + list(_lib._HEADERS)
+    deps = [_SRC, os.path.join(_HERE, "prim_entries.h"), os.path.join(_HERE, "model_entries.h"), os.path.join(_HERE, "op_entries.h")] + [_unit_src(u) for u in _UNITS] + list(_lib._HEADERS)
     newest = max(os.path.getmtime(p) for p in deps)
     os.makedirs(_OBJ_DIR, exist_ok=True)
     objs = [os.path.join(_OBJ_DIR, u[0] + ".o") for u in _UNITS]
@@ -100,6 +100,31 @@ class Prims:
         assert rc == 0, (rc, kind, p, nF, bw)
         torch.cuda.synchronize()
         return {"x": tx.cpu().numpy(), "M": tM.cpu().numpy(), "aux": taux.cpu().numpy(), "fail": tfail.cpu().numpy()}
+
+    def model_run(self, kind, H, theta, g, nF, reg_rel=0.0, ord_=None, seed=0, nomfma=False):
+        """the contract of emul_lib.model_run_host, on cuda:0 (seed: ignored, the hardware schedules)"""
+        import torch
+
+        import emul_lib as E
+
+        dev = torch.device("cuda:0")
+        k = E.PRIM_KINDS[kind]
+        ins, out, m = E.model_buffers(kind, H, theta, g, ord_, nF)
+        B, p = ins["theta"].shape
+        hs = int(self.lib.cave_prims_info(C.c_int32(k), C.c_int32(0), C.c_int32(p), C.c_int32(nF), C.c_int32(0)))
+        assert hs >= 0 and ins["H"].shape[1] == hs, (kind, p, nF, ins["H"].shape, hs)
+        assert not nomfma or kind.startswith("dense_model")
+        ti = {n: torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(dev) for n, a in ins.items()}  # (same bits)
+        to = {n: torch.from_numpy(a).to(dev) for n, a in out.items()}
+        a = E.PrimBatch(B=B, p=p, nF=nF, bw=0, n_ex=0, reg_rel=reg_rel, H=ti["H"].data_ptr(), h_stride=hs, M=to["M"].data_ptr(),
+                        m_stride=m, theta=ti["theta"].data_ptr(), g=ti["g"].data_ptr(), ord=ti["ord"].data_ptr(),
+                        tc=to["tc"].data_ptr(), moved=to["moved"].data_ptr(), sact_out=to["sact"].data_ptr(),
+                        ss_out=to["ss"].data_ptr())
+        fn = self.lib.cave_prims_run_nomfma if nomfma else self.lib.cave_prims_run
+        rc = fn(C.c_int32(k), C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        assert rc == 0, (rc, kind, p, nF)
+        torch.cuda.synchronize()
+        return {n: t.cpu().numpy() for n, t in to.items()}
 
     def op_run(self, op, ctx, pm1, cases, seed=0):
         """the contract of emul_lib.op_run_host, on cuda:0 (seed: ignored, the hardware schedules)"""
