@@ -18,12 +18,12 @@ _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.path.join(_HERE, "libcave_hip.so")
 _CSRC = os.path.join(_HERE, "csrc")
 _HEADERS = [os.path.join(_CSRC, n) for n in ("kernels.h", "cone_common.h", "cone_core.h", "cone_band.h", "cone_dense.h", "cone_rb.h", "cone_instance.h", "cone_step.h",
-                                             "wave_prims.h", "ctx_wave.h", "ctx_block.h", "solver_entry.h", "sp_grid.h", "tsp_hk.h", "vrp_dp.h", "tsp_hk_wide.h")] + \
+                                             "wave_prims.h", "ctx_wave.h", "ctx_block.h", "solver_entry.h", "sp_grid.h", "tsp_hk.h", "vrp_dp.h", "tsp_hk_wide.h", "vrp_dp_wide.h")] + \
     [os.path.join(_ROOT, "include", "cave_hip.h")]
 # translation units: the C ABI (host code) + one file per kernel shape (cave_amd/csrc/kernels.h)
 _UNITS = ["cave_hip"] + [f"k_{op}_w{w}" for op in ("dense", "pack", "packed") for w in (1, 2, 4, 8)] + \
     ["k_large_dense", "k_large_pack", "k_large_packed_w1", "k_large_packed_w2", "k_large_packed_w4", "k_step",
-     "k_step_warm", "k_step_sparse", "k_step_sparse_warm", "k_step_ipm", "k_step_sparse_ipm", "k_pack_sparse_w2", "k_pack_sparse_w4", "k_pack_sparse_w8", "k_large_pack_sparse", "k_sp_grid", "k_tsp_hk", "k_vrp_dp", "k_tsp_hk_wide"]
+     "k_step_warm", "k_step_sparse", "k_step_sparse_warm", "k_step_ipm", "k_step_sparse_ipm", "k_pack_sparse_w2", "k_pack_sparse_w4", "k_pack_sparse_w8", "k_large_pack_sparse", "k_sp_grid", "k_tsp_hk", "k_vrp_dp", "k_tsp_hk_wide", "k_vrp_dp_wide"]
 _SOURCES = [os.path.join(_CSRC, u + ".hip") for u in _UNITS] + _HEADERS
 _OBJ_DIR = os.path.join(_CSRC, "build")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
@@ -46,6 +46,7 @@ ABI_SYMBOLS = (
     "cave_hip_tsp_hk_slot_bytes", "cave_hip_tsp_hk_workspace_bytes", "cave_hip_tsp_hk_solve",
     "cave_hip_vrp_dp_slot_bytes", "cave_hip_vrp_dp_workspace_bytes", "cave_hip_vrp_dp_solve",
     "cave_hip_tsp_hk_wide_slot_bytes", "cave_hip_tsp_hk_wide_workspace_bytes", "cave_hip_tsp_hk_wide_solve",
+    "cave_hip_vrp_dp_wide_slot_bytes", "cave_hip_vrp_dp_wide_workspace_bytes", "cave_hip_vrp_dp_wide_solve",
 )
 
 
@@ -240,6 +241,11 @@ def load_library() -> C.CDLL:
     lib.cave_hip_vrp_dp_slot_bytes.restype = lib.cave_hip_vrp_dp_workspace_bytes.restype = i64
     lib.cave_hip_vrp_dp_solve.argtypes = [vp, vp, vp, C.c_double, i64, i64, i64, vp, vp, vp, vp, vp, vp, i64, vp]
     lib.cave_hip_vrp_dp_solve.restype = i32
+    lib.cave_hip_vrp_dp_wide_slot_bytes.argtypes = [i64, i64]
+    lib.cave_hip_vrp_dp_wide_workspace_bytes.argtypes = [i64, i64, i64]
+    lib.cave_hip_vrp_dp_wide_slot_bytes.restype = lib.cave_hip_vrp_dp_wide_workspace_bytes.restype = i64
+    lib.cave_hip_vrp_dp_wide_solve.argtypes = [vp, vp, vp, C.c_double, i64, i64, i64, vp, vp, vp, vp, vp, vp, i64, vp]
+    lib.cave_hip_vrp_dp_wide_solve.restype = i32
     _lib = lib
     return lib
 

@@ -12,6 +12,7 @@
 #include "tsp_hk.h"
 #include "tsp_hk_wide.h"
 #include "vrp_dp.h"
+#include "vrp_dp_wide.h"
 
 namespace cave {
 
@@ -690,6 +691,34 @@ int32_t cave_hip_tsp_hk_wide_solve(const float* costs, const float* eval_costs, 
   if (grid == 0) return CAVE_OK;
   hipError_t e = launch_tsp_hk_wide((unsigned)grid, (hipStream_t)stream, P);
   if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch tsp_hk_wide kernels", e);
+  return CAVE_OK;
+}
+
+// ------------------------------------------------------------------ CVRP dynamic program, 13 <= n <= 20 (vrp_dp_wide.h)
+
+int64_t cave_hip_vrp_dp_wide_slot_bytes(int64_t n, int64_t K) {
+  if (!vrp_dp_wide_valid(n, K)) return fail(CAVE_E_INVALID, "vrp_dp_wide_slot_bytes: need 13 <= n <= 20 and 1 <= K <= 8");
+  return vrp_dp_wide_slot_bytes(n, K);
+}
+
+int64_t cave_hip_vrp_dp_wide_workspace_bytes(int64_t n, int64_t K, int64_t N) {
+  if (!vrp_dp_wide_valid(n, K) || N < 0)
+    return fail(CAVE_E_INVALID, "vrp_dp_wide_workspace_bytes: need 13 <= n <= 20, 1 <= K <= 8 and N >= 0");
+  return solver_workspace_bytes(tsp_hk_wide_header_bytes(n), vrp_dp_wide_slot_bytes(n, K), N, vrp_dp_wide_default_slots(n, K));
+}
+
+int32_t cave_hip_vrp_dp_wide_solve(const float* costs, const float* eval_costs, const float* demands, double capacity, int64_t K,
+                                   int64_t N, int64_t n, float* sol, double* obj, double* eval, int32_t* routes, int32_t* status,
+                                   void* workspace, int64_t workspace_bytes, void* stream) {
+  VrpDpWideParams P;
+  int64_t grid;
+  char msg[kSolverMsg];
+  const int32_t rc = vrp_dp_wide_plan(costs, eval_costs, demands, capacity, K, N, n, sol, obj, eval, routes, status, workspace,
+                                      workspace_bytes, &P, &grid, msg);
+  if (rc != CAVE_OK) return fail(rc, msg);
+  if (grid == 0) return CAVE_OK;
+  hipError_t e = launch_vrp_dp_wide((unsigned)grid, (hipStream_t)stream, P);
+  if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch vrp_dp_wide kernels", e);
   return CAVE_OK;
 }
 

@@ -1,9 +1,9 @@
 // solver_entry.h — the host side the exact-solver entry points share (cave_hip_sp_grid_solve, cave_hip_tsp_hk_solve,
-// cave_hip_vrp_dp_solve, cave_hip_tsp_hk_wide_solve): the argument checks, the grid rule and the default workspace.
-// Plain host code: the C ABI (cave_hip.hip) and the emulation drivers (tests/emul/simt_*.cpp, g++) call the same
-// functions, so the CPU tier runs the checks the library runs.  Each entry's own plan function (sp_grid_plan,
-// tsp_hk_plan, vrp_dp_plan, tsp_hk_wide_plan, beside its layout functions) states what is its own -- the shape rule, its
-// messages, its sizes -- and fills its parameter block.
+// cave_hip_vrp_dp_solve, cave_hip_tsp_hk_wide_solve, cave_hip_vrp_dp_wide_solve): the argument checks, the grid rule and
+// the default workspace.  Plain host code: the C ABI (cave_hip.hip) and the emulation drivers (tests/emul/simt_*.cpp, g++)
+// call the same functions, so the CPU tier runs the checks the library runs.  Each entry's own plan function
+// (sp_grid_plan, tsp_hk_plan, vrp_dp_plan, tsp_hk_wide_plan, vrp_dp_wide_plan, beside its layout functions) states what
+// is its own -- the shape rule, its messages, its sizes -- and fills its parameter block.
 #pragma once
 #include <stdint.h>
 #include <stdio.h>

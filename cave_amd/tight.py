@@ -43,8 +43,9 @@ rounded-capacity cuts): the optimum comes from a dynamic program on top of the H
 through a customer set costs its Held-Karp path plus the closing edge, a set-partition recurrence over the subsets picks
 the routes), the cuts from the rule of the reference's callback applied to the successive optima of the cut relaxation
 (`vrp_rcc_cuts`), the tight rows as for the TSP (`vrp_tight_normals`).  The dynamic program also runs on the device, one
-workgroup per instance (`vrp_solve_hip`; cave_amd/csrc/vrp_dp.h), bit for bit; `VRPConeDataset(..., device=...)` and
-`vrp_regret(..., device=...)` use it.  The cut loop stays on the host.
+workgroup per instance (`vrp_solve_hip`; cave_amd/csrc/vrp_dp.h), bit for bit, and from 13 to 20 nodes with its tables in
+device memory (`vrp_solve_hip_wide`; cave_amd/csrc/vrp_dp_wide.h); `VRPConeDataset(..., device=...)` and
+`vrp_regret(..., device=...)` use the first up to 14 nodes and the second beyond.  The cut loop stays on the host.
 """
 
 from __future__ import annotations
@@ -56,7 +57,8 @@ from .synth import sp_arcs
 __all__ = ["sp_solve", "sp_tight_normals", "sp_gen_data", "SPConeDataset", "sp_regret", "sp_solve_hip", "sp_cones_hip",
            "tsp_solve", "tsp_dfj_cuts", "tsp_tight_normals", "tsp_gen_data", "TSPConeDataset", "tsp_regret", "tsp_solve_hip",
            "tsp_solve_hip_wide",
-           "vrp_solve", "vrp_rcc_cuts", "vrp_tight_normals", "vrp_gen_data", "VRPConeDataset", "vrp_regret", "vrp_solve_hip"]
+           "vrp_solve", "vrp_rcc_cuts", "vrp_tight_normals", "vrp_gen_data", "VRPConeDataset", "vrp_regret", "vrp_solve_hip",
+           "vrp_solve_hip_wide"]
 
 
 def sp_solve(cost: np.ndarray, h: int, w: int):
@@ -711,6 +713,41 @@ def vrp_gen_data(num_data: int, num_feat: int, n: int, deg: int = 4, noise_width
     return feats, costs, demands
 
 
+def _vrp_dp_hip(who: str, entry: str, lo: int, hi: int, costs, n: int, demands, capacity: float, num_vehicle: int, eval_costs):
+    """`vrp_solve_hip` and `vrp_solve_hip_wide`: the checks, the routes, the demands on the device and the launch of
+    cave_hip_<entry>_solve."""
+    import torch
+
+    from . import _lib
+
+    _lib.load()  # (no device: ImportError before any check of the arguments)
+    n, K = int(n), int(num_vehicle)
+    if not lo <= n <= hi:
+        raise ValueError(f"{who}: the dynamic program on the device takes {lo} <= n <= {hi} nodes, not {n}")
+    if not 1 <= K <= 8:
+        raise ValueError(f"{who}: 1 <= num_vehicle <= 8, not {K}")
+    capacity = float(capacity)
+    if not (np.isfinite(capacity) and capacity > 0):
+        raise ValueError(f"{who}: capacity must be finite and positive")
+    d = n * (n - 1) // 2
+
+    def own(N, dev):  # the routes, and the demands on the device
+        q = demands if isinstance(demands, torch.Tensor) else torch.from_numpy(np.array(demands, dtype=np.float32))
+        q = q.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        if q.numel() != n - 1:
+            raise ValueError(f"{who}: {n - 1} customers, {q.numel()} demands")
+        return [torch.empty(N, n + K, dtype=torch.int32, device=dev), q]
+
+    sols, objs, evals, bad, status, (routes, _) = _hip_solve(
+        who, entry, costs, eval_costs, d, f"a CVRP on {n} nodes has {d} edges", own, (n, K),
+        lambda solve, c, e, N, s, o, ev, st, x, ws, wsb, stream: solve(c, e, x[1], capacity, K, N, n, s, o, ev, x[0], st, ws, wsb, stream))
+    if bad is not None:
+        if int(status[bad]) == _lib.ST_INFEASIBLE:
+            raise ValueError(f"{who}: instance {bad} is infeasible (no partition into feasible routes)")
+        raise ValueError(f"{who}: instance {bad} has a non-finite cost, or a demand is negative or non-finite")
+    return (sols, objs, routes) if eval_costs is None else (sols, objs, routes, evals)
+
+
 def vrp_solve_hip(costs, n: int, demands, capacity: float, num_vehicle: int, eval_costs=None):
     """`vrp_solve` for a batch on the device: costs (N, d) float32, d = n (n-1) / 2, 3 <= n <= 14, demands (n-1,) shared
     by the batch (taken as float32), 1 <= num_vehicle <= 8 -> (sols (N, d) float32 0/1, objs (N,) float64, routes
@@ -719,41 +756,30 @@ def vrp_solve_hip(costs, n: int, demands, capacity: float, num_vehicle: int, eva
     numerator; the fp64 sum of their edges in route order).  Tables that do not fit the LDS lie in a workspace that is
     allocated here for the call (at most 512 slots).  A non-finite cost, a negative or non-finite demand or an
     infeasible instance raises ValueError."""
-    import torch
+    return _vrp_dp_hip("vrp_solve_hip", "vrp_dp", 3, 14, costs, n, demands, capacity, num_vehicle, eval_costs)
 
-    from . import _lib
 
-    _lib.load()  # (no device: ImportError before any check of the arguments)
-    n, K = int(n), int(num_vehicle)
-    if not 3 <= n <= 14:
-        raise ValueError(f"vrp_solve_hip: the dynamic program on the device takes 3 <= n <= 14 nodes, not {n}")
-    if not 1 <= K <= 8:
-        raise ValueError(f"vrp_solve_hip: 1 <= num_vehicle <= 8, not {K}")
-    capacity = float(capacity)
-    if not (np.isfinite(capacity) and capacity > 0):
-        raise ValueError("vrp_solve_hip: capacity must be finite and positive")
-    d = n * (n - 1) // 2
+def vrp_solve_hip_wide(costs, n: int, demands, capacity: float, num_vehicle: int, eval_costs=None):
+    """`vrp_solve_hip` for 13 <= n <= 20 (cave_hip_vrp_dp_wide_solve, cave_amd/csrc/vrp_dp_wide.h): the same arguments,
+    checks, results and errors, the same recurrences bit for bit -- beyond the host solver's 14 nodes, what `vrp_solve`
+    would return if it went that far.  The tables always lie in a workspace that is allocated here for the call: one
+    slot per workgroup of (n-1) 2^(n-2) doubles for the Held-Karp table and (min(K, (n-1)/2) - 1) 2^(n-1) doubles for the
+    route costs and the stored layers (39.8 MB + 4.2 MB per layer at n = 20), min(N, 512, 8 GiB / slot) of them, behind a
+    4 * 2^(n-1)-byte list.  The work of a stored layer is 3^(n-1) / 2 table pairs per instance: none at K = 2, one layer
+    at K = 3."""
+    return _vrp_dp_hip("vrp_solve_hip_wide", "vrp_dp_wide", 13, 20, costs, n, demands, capacity, num_vehicle, eval_costs)
 
-    def own(N, dev):  # the routes, and the demands on the device
-        q = demands if isinstance(demands, torch.Tensor) else torch.from_numpy(np.array(demands, dtype=np.float32))
-        q = q.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
-        if q.numel() != n - 1:
-            raise ValueError(f"vrp_solve_hip: {n - 1} customers, {q.numel()} demands")
-        return [torch.empty(N, n + K, dtype=torch.int32, device=dev), q]
 
-    sols, objs, evals, bad, status, (routes, _) = _hip_solve(
-        "vrp_solve_hip", "vrp_dp", costs, eval_costs, d, f"a CVRP on {n} nodes has {d} edges", own, (n, K),
-        lambda solve, c, e, N, s, o, ev, st, x, ws, wsb, stream: solve(c, e, x[1], capacity, K, N, n, s, o, ev, x[0], st, ws, wsb, stream))
-    if bad is not None:
-        if int(status[bad]) == _lib.ST_INFEASIBLE:
-            raise ValueError(f"vrp_solve_hip: instance {bad} is infeasible (no partition into feasible routes)")
-        raise ValueError(f"vrp_solve_hip: instance {bad} has a non-finite cost, or a demand is negative or non-finite")
-    return (sols, objs, routes) if eval_costs is None else (sols, objs, routes, evals)
+def _vrp_solve_hip_for(n: int):
+    """the device entry `vrp_regret(device=)` and `VRPConeDataset(device=)` take: the first tier up to 14 nodes, the wide
+    one from 15 to 20"""
+    return vrp_solve_hip if int(n) <= 14 else vrp_solve_hip_wide
 
 
 class VRPConeDataset:
     """`optDatasetConstrs` (src/dataset.py:26-130) for the reference's `vrpModel` without Gurobi: sols and objs from the
-    dynamic program (`vrp_solve`; on the device with `device`, `vrp_solve_hip`), cuts from the cutting loop
+    dynamic program (`vrp_solve`; on the device with `device`, `vrp_solve_hip` up to 14 nodes and `vrp_solve_hip_wide`
+    from 15 to 20, beyond the host solver's reach), cuts from the cutting loop
     (`vrp_rcc_cuts`, host), rows those tight at the dynamic program's vertex -- a cut is a valid inequality, so it is a
     valid generator at any vertex where it is tight.  An infeasible instance raises ValueError, as the reference does
     without `skip_infeas`."""
@@ -765,7 +791,7 @@ class VRPConeDataset:
         self.demands = np.asarray(demands, dtype=np.float32).reshape(-1)
         costs = np.asarray(costs, dtype=np.float32)
         if device is not None:
-            s, o, _ = vrp_solve_hip(torch.as_tensor(costs).to(torch.device(device)), n, self.demands, capacity, num_vehicle)
+            s, o, _ = _vrp_solve_hip_for(n)(torch.as_tensor(costs).to(torch.device(device)), n, self.demands, capacity, num_vehicle)
             sols, objs = list(s.cpu().numpy()), [[float(v)] for v in o.cpu().numpy()]
         else:
             sols, objs = [], []
@@ -798,10 +824,12 @@ def vrp_regret(pred_costs: np.ndarray, true_costs: np.ndarray, true_objs: np.nda
     """Normalised regret sum(c . w(c_hat) - z*) / sum(z*) with w(.) from `vrp_solve`.
 
     With `device`: arrays or tensors, moved to the device if they are not there; solved and priced there in one launch
-    (fp64 sums), only the scalar comes back."""
+    (fp64 sums), only the scalar comes back.  Up to 14 nodes through `vrp_solve_hip`, 15 to 20 through
+    `vrp_solve_hip_wide`; without a device the host solver's limit of 14 nodes holds."""
     demands = np.asarray(demands.detach().cpu() if hasattr(demands, "detach") else demands, dtype=np.float32).reshape(-1)
     if device is not None:
-        return _regret_hip(lambda cp, c: vrp_solve_hip(cp, n, demands, capacity, num_vehicle, eval_costs=c)[3], pred_costs, true_costs,
+        solve = _vrp_solve_hip_for(n)
+        return _regret_hip(lambda cp, c: solve(cp, n, demands, capacity, num_vehicle, eval_costs=c)[3], pred_costs, true_costs,
                            true_objs, device)
     loss = 0.0
     for cp, c, z in zip(pred_costs, true_costs, true_objs):

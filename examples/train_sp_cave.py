@@ -16,6 +16,7 @@ reference's CVRP model (2-degree rows, rounded-capacity cuts), solved by the dyn
     python examples/train_sp_cave.py --problem tsp --nodes 12 --packed --device-regret  # the regret's Held-Karp solves run on the device
     python examples/train_sp_cave.py --problem tsp --nodes 20 --num-data 64 --packed --device-regret  # TSP-20: above 14 nodes only the device solves exactly
     python examples/train_sp_cave.py --problem vrp --nodes 10 --capacity 30 --vehicles 3 --packed --device-regret --device-data  # CVRP: solved on the device
+    python examples/train_sp_cave.py --problem vrp --nodes 16 --capacity 40 --vehicles 3 --num-data 32 --packed --device-regret --device-data  # CVRP-15: above 14 nodes only the device solves exactly
 """
 
 import argparse
@@ -42,7 +43,9 @@ def main(argv=None):
     ap.add_argument("--packed", action="store_true", help="device-resident packed cones instead of dense padding")
     ap.add_argument("--problem", default="sp", choices=["sp", "tsp", "vrp"])
     ap.add_argument("--nodes", type=int, default=10, help="TSP / CVRP size, the depot included (Held-Karp: <= 14; the TSP up to 20 with --device-regret, "
-                                                              "the device's wide Held-Karp tier)")
+                                                              "the device's wide Held-Karp tier; the CVRP up to 20 with --device-regret "
+                                                              "AND --device-data, the device's wide CVRP tier: above 14 nodes no host "
+                                                              "solver reaches the data set's optima or the regret's)")
     ap.add_argument("--capacity", type=float, default=30.0, help="CVRP: vehicle capacity (demands are uniform on [0, 10))")
     ap.add_argument("--vehicles", type=int, default=3, help="CVRP: number of vehicles")
     ap.add_argument("--inner", default="push", choices=["push", "ipm"],
@@ -79,6 +82,10 @@ def main(argv=None):
     if args.problem == "tsp" and args.nodes > 14 and not (args.nodes <= 20 and args.device_regret):
         ap.error("--problem tsp takes --nodes up to 20, and above 14 nodes it needs --device-regret: the host's Held-Karp stops "
                  "at 14 nodes, the regret's exact tours then come from the device (tsp_regret(..., device=))")
+    if args.problem == "vrp" and args.nodes > 14 and not (args.nodes <= 20 and args.device_regret and args.device_data):
+        ap.error("--problem vrp takes --nodes up to 20, and above 14 nodes it needs --device-regret and --device-data: the host's "
+                 "dynamic program stops at 14 nodes, the data set's optima and the regret's exact routes then come from the device "
+                 "(VRPConeDataset(..., device=), vrp_regret(..., device=))")
     sp_device = args.device_data and args.problem == "sp"
     if args.graph and (not args.packed or args.variant == "hybrid"):
         ap.error("--graph needs --packed and a variant without a per-call branch draw")

@@ -54,7 +54,7 @@ extern "C" {
 #define CAVE_ST_NOT_CONVERGED 1 /* iteration cap reached (SciPy raises RuntimeError, src/cave.py:307) */
 #define CAVE_ST_TOO_LARGE 2     /* cone did not fit this launch's LDS arena; retry with larger limits */
 #define CAVE_ST_BAD_INPUT 3     /* non-finite values; sparse wire format: an entry that breaks its contract */
-#define CAVE_ST_INFEASIBLE 4    /* cave_hip_vrp_dp_solve: the instance has no feasible solution */
+#define CAVE_ST_INFEASIBLE 4    /* cave_hip_vrp_dp[_wide]_solve: the instance has no feasible solution */
 
 /* modes */
 #define CAVE_MODE_PROJECT 0
@@ -545,6 +545,31 @@ int64_t cave_hip_tsp_hk_wide_workspace_bytes(int64_t n, int64_t N);
 int32_t cave_hip_tsp_hk_wide_solve(const float* costs, const float* eval_costs, int64_t N, int64_t n, float* sol, double* obj,
                                    double* eval, int32_t* tour, int32_t* status, void* workspace, int64_t workspace_bytes,
                                    void* stream);
+
+/* ------------------------------------------------------------------ CVRP dynamic program, wide tier (additive to v10)
+ * The CVRP section above for 13 <= n <= 20 and 1 <= K <= 8: the same problem, arguments (in the same order), outputs,
+ * recurrences (bit for bit the same results; at n = 13, 14 the bytes cave_hip_vrp_dp_solve writes) and failure
+ * semantics, with tables that always lie in the caller's workspace: one 512-thread workgroup per slot, workgroups
+ * striding over the N instances.
+ *   workspace   a device buffer of workspace_bytes bytes, 8-byte aligned: a header region of 4 * 2^(n-1) bytes (filled
+ *               on every call by a small kernel in front of the dynamic program, same stream) followed by slots of
+ *               slot_bytes = 8 (n-1) 2^(n-2) + 8 (min(K, (n-1)/2) - 1) 2^(n-1) bytes (the Held-Karp table, then r and
+ *               the stored layers: 39845888 + 4194304 (min(K, 9) - 1) at n = 20), at least one.  The launch uses
+ *               min(N, (workspace_bytes - header) / slot_bytes) workgroups.  Its contents on entry do not matter and
+ *               mean nothing afterwards; two calls that may run at the same time need a workspace each.
+ * No state between calls.  N == 0: nothing to do, CAVE_OK (no workspace needed).
+ * CAVE_E_INVALID before any launch, nothing written: n < 13 or n > 20, K < 1 or K > 8; eval without eval_costs; a
+ * capacity that is not finite and positive; with N > 0 a NULL or misaligned workspace or one smaller than the header
+ * region plus one slot, or a NULL costs or demands.
+ * cave_hip_vrp_dp_wide_slot_bytes: the bytes of one slot.
+ * cave_hip_vrp_dp_wide_workspace_bytes: header + slot_bytes * min(N, 512, floor(8 GiB / slot_bytes)), the default
+ * workspace -- a default, not a limit.  Both return CAVE_E_INVALID for an n or K out of range (the second also for
+ * N < 0). */
+int64_t cave_hip_vrp_dp_wide_slot_bytes(int64_t n, int64_t K);
+int64_t cave_hip_vrp_dp_wide_workspace_bytes(int64_t n, int64_t K, int64_t N);
+int32_t cave_hip_vrp_dp_wide_solve(const float* costs, const float* eval_costs, const float* demands, double capacity,
+                                   int64_t K, int64_t N, int64_t n, float* sol, double* obj, double* eval,
+                                   int32_t* routes, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
