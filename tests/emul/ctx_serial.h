@@ -7,6 +7,13 @@
 #include <string.h>
 #include "../../cave_amd/csrc/cone_common.h"
 
+// HIP's vector type: cone_step.h (included for cone_entry.h's fills) names it in its templates.  The serial build never
+// sees a <hip/hip_runtime.h>, the real one or the SIMT shim's, which define it themselves: refuse the combination.
+#if defined(CAVE_SIMT_EMUL) || defined(__HIPCC__)
+#error "ctx_serial.h is for the serial g++ build only"
+#endif
+struct uint4 { unsigned x, y, z, w; };
+
 namespace cave {
 
 struct SerialCtx {

@@ -10,6 +10,7 @@
 #include "ctx_serial.h"
 #include "../../cave_amd/csrc/cone_core.h"
 #include "../../cave_amd/csrc/cone_instance.h"
+#include "../../cave_amd/csrc/cone_entry.h"
 
 using namespace cave;
 
@@ -31,11 +32,8 @@ int32_t cave_emul_cone_dense(const float* ctrs, const float* pred, int64_t B, in
   // explicit limits are taken as given, even beyond the 160 KiB a real workgroup has: this lets
   // the CPU tier validate the algorithm at sizes (TSP-50) the round-1 kernels cannot hold in LDS yet
   if (!(nnz_cap > 0 && lds_bytes > 0) && !resolve_limits(m_max, d, nnz_cap, lds_bytes)) return CAVE_E_INVALID;
-  DenseParams P;
-  P.ctrs = ctrs; P.pred = pred; P.B = B; P.m = (int32_t)m_max; P.d = (int32_t)d; P.mode = mode;
-  P.sign = sign; P.inner_ratio = inner_ratio; P.max_iter = max_iter > 0 ? max_iter : 100;
-  P.nnz_cap = (uint32_t)nnz_cap; P.lds_bytes = (uint32_t)lds_bytes;
-  P.o = OutPtrs{proj, rnorm, target, loss, grad, status, iters};
+  const DenseParams P = dense_fill(ctrs, pred, B, m_max, d, mode, sign, inner_ratio, max_iter, nnz_cap, lds_bytes,
+                                   OutPtrs{proj, rnorm, target, loss, grad, status, iters});
   std::vector<unsigned char> smem((size_t)lds_bytes);  // exact size: ASan catches arena overruns
   SerialCtx c;
   for (int64_t b = 0; b < B; ++b) run_dense_instance(c, smem.data(), P, b);
@@ -45,11 +43,7 @@ int32_t cave_emul_cone_dense(const float* ctrs, const float* pred, int64_t B, in
 int32_t cave_emul_pack_count(const float* ctrs, int64_t B, int64_t m_max, int64_t d, int32_t nnz_cap,
                              int32_t lds_bytes, int32_t* n_rows, int32_t* n_nnz, int32_t* status) {
   if (!resolve_limits(m_max, d, nnz_cap, lds_bytes)) return CAVE_E_INVALID;
-  PackParams P;
-  memset(&P, 0, sizeof(P));
-  P.ctrs = ctrs; P.B = B; P.m = (int32_t)m_max; P.d = (int32_t)d;
-  P.nnz_cap = (uint32_t)nnz_cap; P.lds_bytes = (uint32_t)lds_bytes;
-  P.n_rows = n_rows; P.n_nnz = n_nnz; P.status = status; P.fill = 0;
+  const PackParams P = pack_fill_params(ctrs, B, m_max, d, nnz_cap, lds_bytes, n_rows, n_nnz, status, nullptr, 0);
   std::vector<unsigned char> smem((size_t)lds_bytes);
   SerialCtx c;
   for (int64_t b = 0; b < B; ++b) run_pack_instance(c, smem.data(), P, b);
@@ -59,12 +53,8 @@ int32_t cave_emul_pack_count(const float* ctrs, int64_t B, int64_t m_max, int64_
 int32_t cave_emul_pack_fill(const float* ctrs, int64_t B, int64_t m_max, int64_t d, int32_t nnz_cap,
                             int32_t lds_bytes, const cave_cone_store* store, int64_t slot0, int32_t* status) {
   if (!resolve_limits(m_max, d, nnz_cap, lds_bytes)) return CAVE_E_INVALID;
-  if (!store || store->d != d || slot0 < 0 || slot0 + B > store->n) return CAVE_E_INVALID;
-  PackParams P;
-  memset(&P, 0, sizeof(P));
-  P.ctrs = ctrs; P.B = B; P.m = (int32_t)m_max; P.d = (int32_t)d;
-  P.nnz_cap = (uint32_t)nnz_cap; P.lds_bytes = (uint32_t)lds_bytes;
-  P.status = status; P.store = *store; P.slot0 = slot0; P.fill = 1;
+  if (!store || !store_slot_ok(store, d, slot0, B)) return CAVE_E_INVALID;
+  const PackParams P = pack_fill_params(ctrs, B, m_max, d, nnz_cap, lds_bytes, nullptr, nullptr, status, store, slot0);
   std::vector<unsigned char> smem((size_t)lds_bytes);
   SerialCtx c;
   for (int64_t b = 0; b < B; ++b) run_pack_instance(c, smem.data(), P, b);
@@ -81,10 +71,8 @@ int32_t cave_emul_cone_packed(const cave_cone_store* store, const int64_t* ids, 
                               float* proj, float* rnorm, float* target, float* loss, float* grad, int32_t* status,
                               int32_t* iters) {
   if (!store || lds_bytes <= 0) return CAVE_E_INVALID;
-  PackedParams P;
-  P.store = *store; P.ids = ids; P.pred = pred; P.B = B; P.mode = mode; P.sign = sign;
-  P.inner_ratio = inner_ratio; P.max_iter = max_iter > 0 ? max_iter : 100; P.lds_bytes = (uint32_t)lds_bytes;
-  P.o = OutPtrs{proj, rnorm, target, loss, grad, status, iters};
+  const PackedParams P = packed_fill(store, ids, pred, B, mode, sign, inner_ratio, max_iter, lds_bytes,
+                                     OutPtrs{proj, rnorm, target, loss, grad, status, iters});
   std::vector<unsigned char> smem((size_t)lds_bytes);
   SerialCtx c;
   for (int64_t b = 0; b < B; ++b) run_packed_instance(c, smem.data(), P, b);
@@ -118,11 +106,8 @@ int32_t cave_emul_cone_dense_large(const float* ctrs, const float* pred, int64_t
                                    int32_t lds_bytes, int64_t slice_bytes, float* proj, float* rnorm, float* target,
                                    float* loss, float* grad, int32_t* status, int32_t* iters) {
   if (nnz_cap <= 0 || lds_bytes <= 0 || slice_bytes <= 0 || slice_bytes >= ((int64_t)1 << 32)) return CAVE_E_INVALID;
-  DenseParams P;
-  P.ctrs = ctrs; P.pred = pred; P.B = B; P.m = (int32_t)m_max; P.d = (int32_t)d; P.mode = mode;
-  P.sign = sign; P.inner_ratio = inner_ratio; P.max_iter = max_iter > 0 ? max_iter : (mode == CAVE_MODE_INNER_IPM ? 3 : 100);
-  P.nnz_cap = (uint32_t)nnz_cap; P.lds_bytes = (uint32_t)lds_bytes;
-  P.o = OutPtrs{proj, rnorm, target, loss, grad, status, iters};
+  const DenseParams P = dense_fill(ctrs, pred, B, m_max, d, mode, sign, inner_ratio, max_iter, nnz_cap, lds_bytes,
+                                   OutPtrs{proj, rnorm, target, loss, grad, status, iters});
   std::vector<unsigned char> smem((size_t)lds_bytes), ws((size_t)slice_bytes);
   SerialCtx c;
   for (int64_t b = 0; b < B; ++b) run_dense_instance<SerialCtx, true>(c, smem.data(), P, b, ws.data(), (uint32_t)slice_bytes);
@@ -133,13 +118,8 @@ int32_t cave_emul_pack_large(const float* ctrs, int64_t B, int64_t m_max, int64_
                              int64_t slice_bytes, int32_t* n_rows, int32_t* n_nnz, const cave_cone_store* store,
                              int64_t slot0, int32_t* status) {
   if (nnz_cap <= 0 || slice_bytes <= 0 || slice_bytes >= ((int64_t)1 << 32)) return CAVE_E_INVALID;
-  if (store && (store->d != d || slot0 < 0 || slot0 + B > store->n)) return CAVE_E_INVALID;
-  PackParams P;
-  memset(&P, 0, sizeof(P));
-  P.ctrs = ctrs; P.B = B; P.m = (int32_t)m_max; P.d = (int32_t)d;
-  P.nnz_cap = (uint32_t)nnz_cap; P.lds_bytes = 1024;
-  P.n_rows = n_rows; P.n_nnz = n_nnz; P.status = status;
-  if (store) { P.store = *store; P.slot0 = slot0; P.fill = 1; }
+  if (store && !store_slot_ok(store, d, slot0, B)) return CAVE_E_INVALID;
+  const PackParams P = pack_fill_params(ctrs, B, m_max, d, nnz_cap, 1024, n_rows, n_nnz, status, store, slot0);
   std::vector<unsigned char> smem(1024), ws((size_t)slice_bytes);
   SerialCtx c;
   for (int64_t b = 0; b < B; ++b) run_pack_instance<SerialCtx, true>(c, smem.data(), P, b, ws.data(), (uint32_t)slice_bytes);
@@ -151,10 +131,8 @@ int32_t cave_emul_cone_packed_large(const cave_cone_store* store, const int64_t*
                                     int64_t slice_bytes, float* proj, float* rnorm, float* target, float* loss,
                                     float* grad, int32_t* status, int32_t* iters) {
   if (!store || lds_bytes <= 0 || slice_bytes <= 0 || slice_bytes >= ((int64_t)1 << 32)) return CAVE_E_INVALID;
-  PackedParams P;
-  P.store = *store; P.ids = ids; P.pred = pred; P.B = B; P.mode = mode; P.sign = sign;
-  P.inner_ratio = inner_ratio; P.max_iter = max_iter > 0 ? max_iter : (mode == CAVE_MODE_INNER_IPM ? 3 : 100); P.lds_bytes = (uint32_t)lds_bytes;
-  P.o = OutPtrs{proj, rnorm, target, loss, grad, status, iters};
+  const PackedParams P = packed_fill(store, ids, pred, B, mode, sign, inner_ratio, max_iter, lds_bytes,
+                                     OutPtrs{proj, rnorm, target, loss, grad, status, iters});
   std::vector<unsigned char> smem((size_t)lds_bytes), ws((size_t)slice_bytes);
   SerialCtx c;
   for (int64_t b = 0; b < B; ++b) run_packed_large_instance<SerialCtx>(c, smem.data(), P, b, ws.data(), (uint32_t)slice_bytes);

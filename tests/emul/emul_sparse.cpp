@@ -9,6 +9,7 @@
 #include "ctx_serial.h"
 #include "../../cave_amd/csrc/cone_core.h"
 #include "../../cave_amd/csrc/cone_instance.h"
+#include "../../cave_amd/csrc/cone_entry.h"
 
 using namespace cave;
 
@@ -17,21 +18,12 @@ static bool sparse_ok(const cave_sparse_cones* s) {
          (s->B == 0 || (s->ent_off && s->key && s->val));
 }
 
-static SparsePackParams sparse_params(const cave_sparse_cones* s, int64_t nnz_cap, int32_t lds_bytes) {
-  SparsePackParams P;
-  memset(&P, 0, sizeof(P));
-  P.ent_off = s->ent_off; P.key = s->key; P.val = s->val; P.B = s->B; P.m = s->m_max; P.d = s->d;
-  P.nnz_cap = (uint32_t)nnz_cap; P.lds_bytes = (uint32_t)lds_bytes;
-  return P;
-}
-
 extern "C" {
 
 int32_t cave_emul_pack_count_sparse(const cave_sparse_cones* cones, int32_t nnz_cap, int32_t lds_bytes, int32_t* n_rows,
                                     int32_t* n_nnz, int32_t* status) {
   if (!sparse_ok(cones) || !resolve_limits(cones->m_max, cones->d, nnz_cap, lds_bytes)) return CAVE_E_INVALID;
-  SparsePackParams P = sparse_params(cones, nnz_cap, lds_bytes);
-  P.n_rows = n_rows; P.n_nnz = n_nnz; P.status = status; P.fill = 0;
+  const SparsePackParams P = sparse_pack_fill(cones, nnz_cap, lds_bytes, n_rows, n_nnz, status, nullptr, 0);
   std::vector<unsigned char> smem((size_t)lds_bytes);  // exact size: ASan catches arena overruns
   SerialCtx c;
   for (int64_t b = 0; b < P.B; ++b) run_pack_sparse_instance(c, smem.data(), P, b);
@@ -41,9 +33,8 @@ int32_t cave_emul_pack_count_sparse(const cave_sparse_cones* cones, int32_t nnz_
 int32_t cave_emul_pack_fill_sparse(const cave_sparse_cones* cones, int32_t nnz_cap, int32_t lds_bytes,
                                    const cave_cone_store* store, int64_t slot0, int32_t* status) {
   if (!sparse_ok(cones) || !resolve_limits(cones->m_max, cones->d, nnz_cap, lds_bytes)) return CAVE_E_INVALID;
-  if (!store || store->d != cones->d || slot0 < 0 || slot0 + cones->B > store->n) return CAVE_E_INVALID;
-  SparsePackParams P = sparse_params(cones, nnz_cap, lds_bytes);
-  P.status = status; P.store = *store; P.slot0 = slot0; P.fill = 1;
+  if (!store || !store_slot_ok(store, cones->d, slot0, cones->B)) return CAVE_E_INVALID;
+  const SparsePackParams P = sparse_pack_fill(cones, nnz_cap, lds_bytes, nullptr, nullptr, status, store, slot0);
   std::vector<unsigned char> smem((size_t)lds_bytes);
   SerialCtx c;
   for (int64_t b = 0; b < P.B; ++b) run_pack_sparse_instance(c, smem.data(), P, b);
@@ -53,10 +44,8 @@ int32_t cave_emul_pack_fill_sparse(const cave_sparse_cones* cones, int32_t nnz_c
 int32_t cave_emul_pack_large_sparse(const cave_sparse_cones* cones, int64_t nnz_cap, int64_t slice_bytes, int32_t* n_rows,
                                     int32_t* n_nnz, const cave_cone_store* store, int64_t slot0, int32_t* status) {
   if (!sparse_ok(cones) || nnz_cap <= 0 || slice_bytes <= 0 || slice_bytes >= ((int64_t)1 << 32)) return CAVE_E_INVALID;
-  if (store && (store->d != cones->d || slot0 < 0 || slot0 + cones->B > store->n)) return CAVE_E_INVALID;
-  SparsePackParams P = sparse_params(cones, nnz_cap, 1024);
-  P.n_rows = n_rows; P.n_nnz = n_nnz; P.status = status;
-  if (store) { P.store = *store; P.slot0 = slot0; P.fill = 1; }
+  if (store && !store_slot_ok(store, cones->d, slot0, cones->B)) return CAVE_E_INVALID;
+  const SparsePackParams P = sparse_pack_fill(cones, nnz_cap, 1024, n_rows, n_nnz, status, store, slot0);
   std::vector<unsigned char> smem(1024), ws((size_t)slice_bytes);
   SerialCtx c;
   for (int64_t b = 0; b < P.B; ++b) run_pack_sparse_instance<SerialCtx, true>(c, smem.data(), P, b, ws.data(), (uint32_t)slice_bytes);

@@ -24,7 +24,8 @@
 #include "../../cave_amd/csrc/ctx_wave.h"
 #include "../../cave_amd/csrc/ctx_block.h"
 #include "../../cave_amd/csrc/cone_instance.h"
-#include "../../cave_amd/csrc/cone_step.h"
+#include "../../cave_amd/csrc/cone_entry.h"
+#include "simt_solver.h"
 #include "../prims/prim_entries.h"
 #ifdef CAVE_SIMT_OPS  // the plain build only: the sanitizer and variant builds keep their compile time
 #include "../prims/op_entries.h"
@@ -43,23 +44,10 @@ using CtxL2 = BlockCtx<2, true>;
 using CtxStep = BlockCtx<2, true>;  // pack half of the step kernel (k_step.hip)
 using CtxSolo = SoloCtx<32, 4>;      // its solve half: one wave
 
-struct Lds {  // exact-size, 16-byte aligned heap block standing in for the workgroup's LDS: ASan sees overruns
-  std::vector<unsigned char> raw;
-  unsigned char* p;
-  explicit Lds(size_t n) : raw(n + 16) {
-    uintptr_t a = (uintptr_t)raw.data();
-    size_t off = (16 - (a & 15)) & 15;
-    p = raw.data() + off;
-    raw.resize(off + n);  // no slack behind the arena
-    p = raw.data() + off;
-    len = n;
-  }
-  size_t len;
-  // LDS is not cleared between workgroups: a block starts on whatever the last one left there.  The step entries
-  // poison the block before every workgroup (0xFF bytes: NaN as a double or float, 65535 as an index), so that a
-  // read of LDS the workgroup has not written shows up as a wrong result instead of a convenient zero
-  void poison() { memset(p, 0xFF, len); }
-};
+// LDS is not cleared between workgroups: a block starts on whatever the last one left there.  The step entries poison
+// the block before every workgroup (0xFF bytes: NaN as a double or float, 65535 as an index), so that a read of LDS the
+// workgroup has not written shows up as a wrong result instead of a convenient zero
+using simt_solver::Lds;
 
 template <class C, class F>
 void launch(int64_t B, unsigned grid, uint64_t seed, F&& body) {  // one workgroup per instance
@@ -158,11 +146,6 @@ int32_t op_impl(const cave_ops::OpCase* cases, int64_t B, uint64_t seed) {
 
 #endif  // CAVE_SIMT_OPS
 
-bool lite_store_ok(const cave_lite_store* s, int64_t need, int64_t d) {  // (as cave_hip.hip)
-  return s && s->n >= need && s->d == d && s->hdr && s->usign && s->avg && s->rowptr && s->ell && s->csr16 && s->rl &&
-         (((uintptr_t)s->ell | (uintptr_t)s->csr16) & 15u) == 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -230,9 +213,7 @@ int32_t cave_simt_step_pack(const float* ctrs, int64_t B, int64_t m_max, int64_t
                             const cave_lite_store* dst, int32_t* status) {
   int32_t cap = 0, lds = 0;
   if (B < 0 || m_max <= 0 || step_limits(m_max, d, cap, lds) != CAVE_OK || !lite_store_ok(dst, B, d)) return CAVE_E_INVALID;
-  StepPackParams Q;
-  Q.ctrs = ctrs; Q.B = B; Q.m = (int32_t)m_max; Q.d = (int32_t)d; Q.nnz_cap = (uint32_t)cap; Q.store = *dst; Q.status = status;
-  Q.lite_pmax = lite_pmax_table((int)d);
+  const StepPackParams Q = step_pack_fill(ctrs, B, m_max, d, cap, dst, status);
   Lds mem((size_t)lds);
   launch<CtxStep>(B, (unsigned)B, seed, [&](int64_t b) {
     if (simt::tid() == 0) mem.poison();
@@ -245,7 +226,7 @@ int32_t cave_simt_step_pack(const float* ctrs, int64_t B, int64_t m_max, int64_t
 }
 
 // solve half.  lds_bytes: LDS of the launch (a value of cave_simt_step_lds_bytes); lds_extra: the warm variant's block
-// behind it (cave_hip.hip: 256 when the residency allows it, else 0).  warm == NULL: the cold kernel.
+// behind it (cone_step.h step_warm_lds_extra: 256 when the residency allows it, else 0).  warm == NULL: the cold kernel.
 int32_t cave_simt_step_solve(const cave_lite_store* solve, const int64_t* ids, const float* pred, int64_t B, int32_t mode,
                              float sign, float inner_ratio, int32_t max_iter, int32_t flags, int32_t lds_bytes,
                              int32_t lds_extra, const cave_warm_cache* warm, const int64_t* keys, uint8_t* warm_hit,
@@ -254,30 +235,24 @@ int32_t cave_simt_step_solve(const cave_lite_store* solve, const int64_t* ids, c
   if (B < 0 || mode < CAVE_MODE_PROJECT || mode > CAVE_MODE_AVG || (!pred && mode != CAVE_MODE_AVG)) return CAVE_E_INVALID;
   if (!solve || !lite_store_ok(solve, ids ? 1 : B, solve->d)) return CAVE_E_INVALID;
   if (lds_bytes <= (int32_t)kStepElectBytes || lds_extra < 0) return CAVE_E_INVALID;
-  StepSolveParams P;
-  P.store = *solve; P.ids = ids; P.pred = pred; P.B = B; P.mode = mode; P.sign = sign; P.inner_ratio = inner_ratio;
-  P.max_iter = max_iter > 0 ? max_iter : 100;
-  P.flags = flags;
-  P.o = OutPtrs{proj, rnorm, target, loss, grad, status, iters};
-  StepWarm W{};
+  const StepSolveParams P = step_solve_fill(solve, ids, pred, B, mode, sign, inner_ratio, max_iter, flags,
+                                            OutPtrs{proj, rnorm, target, loss, grad, status, iters}, false);
   if (warm) {
-    const int64_t n = warm->n_entries;
-    if (n <= 0 || (n & (n - 1)) != 0 || !warm->key || !warm->theta || ((uintptr_t)warm->theta & 15u) != 0) return CAVE_E_INVALID;
-    W.key = warm->key; W.theta = warm->theta; W.n = n; W.keys = keys; W.hit = warm_hit; W.lds_extra = (uint32_t)lds_extra;
-    step_solve_impl<true>(P, W, (uint32_t)lds_bytes, (uint32_t)lds_extra, seed);
+    if (warm_cache_bad(warm)) return CAVE_E_INVALID;
+    step_solve_impl<true>(P, step_warm_fill(warm, keys, warm_hit, (uint32_t)lds_extra), (uint32_t)lds_bytes, (uint32_t)lds_extra, seed);
   } else {
     if (warm_hit) memset(warm_hit, 0, (size_t)B);
-    step_solve_impl<false>(P, W, (uint32_t)lds_bytes, 0u, seed);
+    step_solve_impl<false>(P, StepWarm{}, (uint32_t)lds_bytes, 0u, seed);
   }
   return CAVE_OK;
 }
 
 // slot i of `dst` from slot i of the packed store `src` (lite_from_packed_kernel<Ctx2>)
 int32_t cave_simt_lite_from_packed(const cave_cone_store* src, const cave_lite_store* dst, int32_t* status, uint64_t seed) {
-  if (!src || !dst || src->n < 0 || src->d <= 0 || src->d > kLiteMaxD || !lite_store_ok(dst, src->n, src->d)) return CAVE_E_INVALID;
-  LiteFromPackedParams P;
-  P.src = *src; P.dst = *dst; P.n = src->n; P.lds_bytes = lite_from_packed_lds_bytes(src->d); P.status = status;
-  P.lite_pmax = lite_pmax_table((int)src->d);
+  ConePlan<LiteFromPackedParams> L;  // the library's own checks
+  if (lite_from_packed_plan(src, dst, status, &L) != CAVE_OK) return CAVE_E_INVALID;
+  const LiteFromPackedParams& P = L.params;
+  if (L.grid == 0) return CAVE_OK;
   Lds mem((size_t)P.lds_bytes);
   launch<Ctx2>(P.n, (unsigned)P.n, seed, [&](int64_t b) {
     if (simt::tid() == 0) mem.poison();
@@ -315,11 +290,8 @@ int32_t cave_simt_cone_dense(const float* ctrs, const float* pred, int64_t B, in
                              int32_t waves, uint64_t seed, float* proj, float* rnorm, float* target, float* loss,
                              float* grad, int32_t* status, int32_t* iters) {
   if (!resolve_limits(m_max, d, nnz_cap, lds_bytes, waves <= 2 && B <= 2048)) return CAVE_E_INVALID;
-  DenseParams P;
-  P.ctrs = ctrs; P.pred = pred; P.B = B; P.m = (int32_t)m_max; P.d = (int32_t)d; P.mode = mode;
-  P.sign = sign; P.inner_ratio = inner_ratio; P.max_iter = max_iter > 0 ? max_iter : (mode == CAVE_MODE_INNER_IPM ? 3 : 100);
-  P.nnz_cap = (uint32_t)nnz_cap; P.lds_bytes = (uint32_t)lds_bytes;
-  P.o = OutPtrs{proj, rnorm, target, loss, grad, status, iters};
+  const DenseParams P = dense_fill(ctrs, pred, B, m_max, d, mode, sign, inner_ratio, max_iter, nnz_cap, lds_bytes,
+                                   OutPtrs{proj, rnorm, target, loss, grad, status, iters});
   switch (waves) {
     case 1: return dense_impl<Ctx1>(P, seed);
     case 2: return dense_impl<Ctx2>(P, seed);
@@ -333,12 +305,7 @@ int32_t cave_simt_pack_fill(const float* ctrs, int64_t B, int64_t m_max, int64_t
                             int32_t waves, uint64_t seed, const cave_cone_store* store, int64_t slot0, int32_t* n_rows,
                             int32_t* n_nnz, int32_t* status) {
   if (!resolve_limits(m_max, d, nnz_cap, lds_bytes, false)) return CAVE_E_INVALID;
-  PackParams P;
-  memset(&P, 0, sizeof(P));
-  P.ctrs = ctrs; P.B = B; P.m = (int32_t)m_max; P.d = (int32_t)d;
-  P.nnz_cap = (uint32_t)nnz_cap; P.lds_bytes = (uint32_t)lds_bytes;
-  P.n_rows = n_rows; P.n_nnz = n_nnz; P.status = status;
-  if (store) { P.store = *store; P.slot0 = slot0; P.fill = 1; }
+  const PackParams P = pack_fill_params(ctrs, B, m_max, d, nnz_cap, lds_bytes, n_rows, n_nnz, status, store, slot0);
   switch (waves) {
     case 1: return pack_impl<Ctx1>(P, seed);
     case 2: return pack_impl<Ctx2>(P, seed);
@@ -353,11 +320,8 @@ int32_t cave_simt_cone_packed(const cave_cone_store* store, const int64_t* ids, 
                               int32_t waves, uint64_t seed, float* proj, float* rnorm, float* target, float* loss,
                               float* grad, int32_t* status, int32_t* iters) {
   if (!store || lds_bytes <= 0) return CAVE_E_INVALID;
-  PackedParams P;
-  P.store = *store; P.ids = ids; P.pred = pred; P.B = B; P.mode = mode; P.sign = sign;
-  P.inner_ratio = inner_ratio; P.max_iter = max_iter > 0 ? max_iter : (mode == CAVE_MODE_INNER_IPM ? 3 : 100);
-  P.lds_bytes = (uint32_t)lds_bytes;
-  P.o = OutPtrs{proj, rnorm, target, loss, grad, status, iters};
+  const PackedParams P = packed_fill(store, ids, pred, B, mode, sign, inner_ratio, max_iter, lds_bytes,
+                                     OutPtrs{proj, rnorm, target, loss, grad, status, iters});
   switch (waves) {
     case 1: return packed_impl<Ctx1>(P, seed);
     case 2: return packed_impl<Ctx2>(P, seed);
@@ -372,11 +336,8 @@ int32_t cave_simt_cone_packed_large(const cave_cone_store* store, const int64_t*
                                     int32_t waves, int64_t slice_bytes, uint64_t seed, float* proj, float* rnorm,
                                     float* target, float* loss, float* grad, int32_t* status, int32_t* iters) {
   if (!store || lds_bytes <= 0 || slice_bytes <= 0 || slice_bytes >= ((int64_t)1 << 32)) return CAVE_E_INVALID;
-  PackedParams P;
-  P.store = *store; P.ids = ids; P.pred = pred; P.B = B; P.mode = mode; P.sign = sign;
-  P.inner_ratio = inner_ratio; P.max_iter = max_iter > 0 ? max_iter : (mode == CAVE_MODE_INNER_IPM ? 3 : 100);
-  P.lds_bytes = (uint32_t)lds_bytes;
-  P.o = OutPtrs{proj, rnorm, target, loss, grad, status, iters};
+  const PackedParams P = packed_fill(store, ids, pred, B, mode, sign, inner_ratio, max_iter, lds_bytes,
+                                     OutPtrs{proj, rnorm, target, loss, grad, status, iters});
   switch (waves) {
     case 1: return packed_large_impl<Ctx1>(P, slice_bytes, seed);
     case 2: return packed_large_impl<CtxL2>(P, slice_bytes, seed);

@@ -18,7 +18,8 @@
 #include "../../cave_amd/csrc/ctx_wave.h"
 #include "../../cave_amd/csrc/ctx_block.h"
 #include "../../cave_amd/csrc/cone_instance.h"
-#include "../../cave_amd/csrc/cone_step.h"
+#include "../../cave_amd/csrc/cone_entry.h"
+#include "simt_solver.h"
 
 using namespace cave;
 
@@ -26,22 +27,7 @@ namespace {
 
 using CtxSolo = SoloCtx<32, 4>;  // the solve half: one wave
 
-struct Lds {  // exact-size, 16-byte aligned heap block standing in for the workgroup's LDS (as simt_abi.cpp): ASan sees overruns
-  std::vector<unsigned char> raw;
-  unsigned char* p;
-  size_t len;
-  explicit Lds(size_t n) : raw(n + 16), len(n) {
-    const size_t off = (16 - ((uintptr_t)raw.data() & 15)) & 15;
-    raw.resize(off + n);  // no slack behind the arena (shrinking keeps the buffer where it is)
-    p = raw.data() + off;
-  }
-  void poison() { memset(p, 0xFF, len); }  // LDS is not cleared between workgroups: NaN as a float, 65535 as an index
-};
-
-bool lite_store_ok(const cave_lite_store* s, int64_t need, int64_t d) {  // (as cave_hip.hip)
-  return s && s->n >= need && s->d == d && s->hdr && s->usign && s->avg && s->rowptr && s->ell && s->csr16 && s->rl &&
-         (((uintptr_t)s->ell | (uintptr_t)s->csr16) & 15u) == 0;
-}
+using simt_solver::Lds;  // exact-size block standing in for the workgroup's LDS, poisoned before every instance
 
 }  // namespace
 
@@ -55,11 +41,8 @@ int32_t cave_simt_step_solve_ipm(const cave_lite_store* solve, const int64_t* id
   if (B < 0 || !pred) return CAVE_E_INVALID;
   if (!solve || !lite_store_ok(solve, ids ? 1 : B, solve->d)) return CAVE_E_INVALID;
   if (lds_bytes <= (int32_t)kStepElectBytes) return CAVE_E_INVALID;
-  StepSolveParams P;
-  P.store = *solve; P.ids = ids; P.pred = pred; P.B = B; P.mode = CAVE_MODE_INNER_IPM; P.sign = sign; P.inner_ratio = 0.0f;
-  P.max_iter = max_iter > 0 ? max_iter : 3;
-  P.flags = flags;
-  P.o = OutPtrs{proj, rnorm, target, loss, grad, status, iters};
+  const StepSolveParams P = step_solve_fill(solve, ids, pred, B, CAVE_MODE_INNER_IPM, sign, 0.0f, max_iter, flags,
+                                            OutPtrs{proj, rnorm, target, loss, grad, status, iters}, true);
   const StepWarm W{};
   Lds mem((size_t)lds_bytes);
   for (int64_t b = 0; b < B; ++b) {  // one wave per instance

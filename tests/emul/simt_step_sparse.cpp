@@ -19,7 +19,8 @@
 #include "../../cave_amd/csrc/ctx_wave.h"
 #include "../../cave_amd/csrc/ctx_block.h"
 #include "../../cave_amd/csrc/cone_instance.h"
-#include "../../cave_amd/csrc/cone_step.h"
+#include "../../cave_amd/csrc/cone_entry.h"
+#include "simt_solver.h"
 
 using namespace cave;
 
@@ -27,22 +28,7 @@ namespace {
 
 using CtxStep = BlockCtx<2, true>;  // pack half of the step kernels (k_step_sparse.hip)
 
-struct Lds {  // exact-size, 16-byte aligned heap block standing in for the workgroup's LDS (as simt_abi.cpp): ASan sees overruns
-  std::vector<unsigned char> raw;
-  unsigned char* p;
-  size_t len;
-  explicit Lds(size_t n) : raw(n + 16), len(n) {
-    const size_t off = (16 - ((uintptr_t)raw.data() & 15)) & 15;
-    raw.resize(off + n);  // no slack behind the arena (shrinking keeps the buffer where it is)
-    p = raw.data() + off;
-  }
-  void poison() { memset(p, 0xFF, len); }  // LDS is not cleared between workgroups: NaN as a float, 65535 as an index
-};
-
-bool lite_store_ok(const cave_lite_store* s, int64_t need, int64_t d) {  // (as cave_hip.hip)
-  return s && s->n >= need && s->d == d && s->hdr && s->usign && s->avg && s->rowptr && s->ell && s->csr16 && s->rl &&
-         (((uintptr_t)s->ell | (uintptr_t)s->csr16) & 15u) == 0;
-}
+using simt_solver::Lds;  // exact-size block standing in for the workgroup's LDS, poisoned before every workgroup
 
 }  // namespace
 
@@ -54,9 +40,7 @@ int32_t cave_simt_step_pack_sparse(const cave_sparse_cones* cones, uint64_t seed
   if (cones->B > 0 && (!cones->ent_off || !cones->key || !cones->val)) return CAVE_E_INVALID;
   int32_t cap = 0, lds = 0;
   if (step_limits(cones->m_max, cones->d, cap, lds) != CAVE_OK || !lite_store_ok(dst, cones->B, cones->d)) return CAVE_E_INVALID;
-  StepSparsePackParams Q;
-  Q.ent_off = cones->ent_off; Q.key = cones->key; Q.val = cones->val; Q.B = cones->B; Q.m = cones->m_max; Q.d = cones->d;
-  Q.nnz_cap = (uint32_t)cap; Q.store = *dst; Q.status = status; Q.lite_pmax = lite_pmax_table((int)cones->d);
+  const StepSparsePackParams Q = step_sparse_pack_fill(cones, cap, dst, status);
   Lds mem((size_t)lds);
   for (int64_t b = 0; b < Q.B; ++b) {  // one workgroup per instance
     simt::run_block(CtxStep::NT, (unsigned)b, (unsigned)Q.B, [&]() {

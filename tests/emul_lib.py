@@ -25,6 +25,8 @@ _DEPS = [
     os.path.join(_HERE, "..", "cave_amd", "csrc", "cone_core.h"),
     os.path.join(_HERE, "..", "cave_amd", "csrc", "cone_common.h"),
     os.path.join(_HERE, "..", "cave_amd", "csrc", "cone_instance.h"),
+    os.path.join(_HERE, "..", "cave_amd", "csrc", "cone_step.h"),
+    os.path.join(_HERE, "..", "cave_amd", "csrc", "cone_entry.h"),
     os.path.join(_HERE, "..", "include", "cave_hip.h"),
 ]
 
@@ -261,10 +263,10 @@ def warm_cache(n):
 # ballot primitives, the one-wave lite solver, the one-/two-wave band elimination, the blocked dense LDL^T --
 # compiled by g++ against a shim <hip/hip_runtime.h> in which every lane is a fiber.  TEST INFRASTRUCTURE ONLY.
 _SIMT_SRC = os.path.join(_HERE, "emul", "simt_abi.cpp")
-_SIMT_DEPS = _DEPS + [_SIMT_SRC, os.path.join(_HERE, "emul", "simt", "hip", "hip_runtime.h"),
+_SIMT_DEPS = _DEPS + [_SIMT_SRC, os.path.join(_HERE, "emul", "simt", "hip", "hip_runtime.h"), os.path.join(_HERE, "emul", "simt_solver.h"),
                       os.path.join(_HERE, "prims", "prim_entries.h"), os.path.join(_HERE, "prims", "model_entries.h"),
                       os.path.join(_HERE, "prims", "op_entries.h")] + [
-    os.path.join(_HERE, "..", "cave_amd", "csrc", n) for n in ("wave_prims.h", "ctx_wave.h", "ctx_block.h", "cone_step.h")]
+    os.path.join(_HERE, "..", "cave_amd", "csrc", n) for n in ("wave_prims.h", "ctx_wave.h", "ctx_block.h")]
 
 
 def build_simt(asan: bool = False, defines: tuple = (), tag: str = "") -> str:
