@@ -265,18 +265,18 @@ def warm_cache(n):
 _SIMT_SRC = os.path.join(_HERE, "emul", "simt_abi.cpp")
 _SIMT_DEPS = _DEPS + [_SIMT_SRC, os.path.join(_HERE, "emul", "simt", "hip", "hip_runtime.h"), os.path.join(_HERE, "emul", "simt_solver.h"),
                       os.path.join(_HERE, "prims", "prim_entries.h"), os.path.join(_HERE, "prims", "model_entries.h"),
-                      os.path.join(_HERE, "prims", "op_entries.h")] + [
+                      os.path.join(_HERE, "prims", "op_entries.h"), os.path.join(_HERE, "prims", "ipm_entries.h")] + [
     os.path.join(_HERE, "..", "cave_amd", "csrc", n) for n in ("wave_prims.h", "ctx_wave.h", "ctx_block.h")]
 
 
-def build_simt(asan: bool = False, defines: tuple = (), tag: str = "") -> str:
+def build_simt(asan: bool = False, defines: tuple = (), tag: str = "", ops: bool = False) -> str:
     """`defines` / `tag`: a variant build (e.g. a tiny spin limit + a withheld hand-over flag) under its own name."""
     out = os.path.join(_HERE, "emul", f"_simt{tag}_asan.so" if asan else f"_simt{tag}.so")
     newest = max(os.path.getmtime(p) for p in _SIMT_DEPS)
     if os.path.exists(out) and os.path.getmtime(out) >= newest:
         return out
     flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer"] if asan else ["-O2"]
-    if not asan and not defines:  # the operators alone (tests/prims/op_entries.h) are compiled into the plain build only
+    if not asan and (not defines or ops):  # the operators alone (tests/prims/op_entries.h): the plain build, or on request
         flags.append("-DCAVE_SIMT_OPS")
     cmd = ["g++", "-std=c++17", "-fPIC", "-shared", "-w", *flags, *["-D" + x for x in defines],
            "-I" + os.path.join(_HERE, "emul", "simt"), _SIMT_SRC, "-o", out]
@@ -289,8 +289,8 @@ class Simt:
     Stores come from Emul.pack / Emul.pack_large (host arrays).  `seed` != 0 shuffles the order in which the lanes
     run between two rendezvous (a hand-over the source does not order then shows up as wrong numbers)."""
 
-    def __init__(self, asan: bool = False, defines: tuple = (), tag: str = ""):
-        self.lib = C.CDLL(build_simt(asan, defines, tag))
+    def __init__(self, asan: bool = False, defines: tuple = (), tag: str = "", ops: bool = False):
+        self.lib = C.CDLL(build_simt(asan, defines, tag, ops))
         self.lib.cave_simt_packed_large_slice_bytes.restype = C.c_int64
 
     def path_counters(self):
@@ -600,7 +600,7 @@ class OpCase(C.Structure):
 OP_KINDS = {n: i for i, n in enumerate((
     "gather", "gather_st", "gather_diet", "refresh", "refresh_rb", "dphi", "dphi_rb", "update", "update_rb", "grad",
     "grad_st", "grad_dense", "weight", "band_h", "dense_h", "epilogue", "lite_gather", "lite_grad", "lite_hess",
-    "lite_hess_ipm"))}
+    "lite_hess_ipm", "ipm_iter", "ipm_lite"))}
 OP_CTX = {"w1": 0, "b2": 1, "b4": 2, "l2": 3, "l4": 4, "solo": 5}
 OP_VIEW = (("mptr", np.uint32), ("mcol", np.uint16), ("mval", np.float32), ("cptr", np.uint32), ("cvar", np.uint16),
            ("cvalc", np.float32), ("usign", np.uint8), ("vkind", np.uint8), ("longrow", np.uint32), ("teamrow", np.uint32),

@@ -74,7 +74,10 @@ enum : int32_t {
                        //   in1 = mu [n_seq]  -> out [n_seq, p ldh + d]: H | wold after every call (upper triangle of H
                        //   starts as NaN poison: it must come back untouched)
   OP_LITE_HESS_IPM = 19,  // lite_build + lite_hessian_ipm   fin = weights [d]             -> out [p ldh]
-  OP_COUNT = 20,
+  OP_IPM_ITER = 20,    // n_seq steps of solve_cone_ipm_impl<C, PM1, false>   (ipm_entries.h)   fin = y
+                       //                 -> out = rho [d] | theta [p] | z [p] | f | iters | status
+  OP_IPM_LITE = 21,    // lite_build + n_seq steps of lite_solve_ipm          (ipm_entries.h)   same outputs
+  OP_COUNT = 22,
 };
 enum : int32_t { CX_W1 = 0, CX_B2 = 1, CX_B4 = 2, CX_L2 = 3, CX_L4 = 4, CX_SOLO = 5, CX_COUNT = 6 };
 
@@ -88,19 +91,22 @@ template <> struct OpCtx<CX_SOLO> { using type = SoloT; };
 constexpr int cx_threads(int cx) { return (cx == CX_B4 || cx == CX_L4) ? 256 : (cx == CX_B2 || cx == CX_L2) ? 128 : 64; }
 constexpr int32_t op_kind(int op, int cx, bool pm1) { return (op * CX_COUNT + cx) * 2 + (pm1 ? 1 : 0); }
 
-constexpr bool op_is_lite(int op) { return op >= OP_LITE_GATHER && op <= OP_LITE_HESS_IPM; }
+constexpr bool op_is_lite(int op) { return (op >= OP_LITE_GATHER && op <= OP_LITE_HESS_IPM) || op == OP_IPM_LITE; }
 // where the cone's index arrays live while the operator runs: LDS (the small-cone kernels) or global memory (the
 // large-cone path reads them with global_* loads: space_cast<1>)
 constexpr bool op_view_in_lds(int op) {
   return !(op == OP_GATHER_ST || op == OP_GATHER_DIET || op == OP_GRAD_ST || op == OP_GRAD_DENSE || op == OP_BAND_H || op == OP_DENSE_H);
 }
 // does the operator leave its result in an LDS vector the body copies out (else it writes global memory itself)
-constexpr bool op_out_in_lds(int op) { return op != OP_BAND_H && op != OP_EPILOGUE && op != OP_LITE_HESS && op != OP_LITE_HESS_IPM; }
+constexpr bool op_out_in_lds(int op) {
+  return op != OP_BAND_H && op != OP_EPILOGUE && op != OP_LITE_HESS && op != OP_LITE_HESS_IPM && op != OP_IPM_ITER && op != OP_IPM_LITE;
+}
 
 // does the operator read y / avg / the float weights
-constexpr bool op_uses_fin(int op) { return op <= OP_GATHER_DIET || op == OP_EPILOGUE || op_is_lite(op); }
+constexpr bool op_uses_fin(int op) { return op <= OP_GATHER_DIET || op == OP_EPILOGUE || op_is_lite(op) || op == OP_IPM_ITER; }
 
 CAVE_HOSTDEV uint32_t lite_arena_bytes(int d, uint32_t nnz) { return lite_lds_bytes(d, nnz) + 64u; }
+CAVE_HOSTDEV uint64_t ipm_work_bytes(int d, int p, bool own_h);  // ipm_entries.h
 
 // LDS of one workgroup: [context scratch 256 | view arrays | usign | vkind | fin | in0..3 | out | work arrays of the op]
 CAVE_HOSTDEV uint32_t op_lds_bytes(int op, bool pm1, const OpCase& k) {
@@ -117,6 +123,7 @@ CAVE_HOSTDEV uint32_t op_lds_bytes(int op, bool pm1, const OpCase& k) {
   if (op == OP_DENSE_H) n += up16(8ull * fold_entries(k.p)) + 2 * up16(2 * p) + up16(4 * p);
   if (op == OP_EPILOGUE) n += up16(8 * (d + 1));
   if (op_is_lite(op)) n += up16(lite_arena_bytes(k.d, (uint32_t)k.nnz)) + up16(8 * (p * (uint64_t)k.ldh + 1)) + up16(4 * (d + 1));
+  if (op == OP_IPM_ITER || op == OP_IPM_LITE) n += ipm_work_bytes(k.d, k.p, op == OP_IPM_ITER);
   return (uint32_t)(n > 0xffffffffull ? 0xffffffffull : n);
 }
 
@@ -141,6 +148,10 @@ __device__ __forceinline__ void cone_scales(C& c, const SolveView& v, double& vm
   vm = c.reduce_max(vm);
   ml = c.reduce_max(ml);
 }
+
+}  // namespace cave_ops
+#include "ipm_entries.h"
+namespace cave_ops {
 
 template <int OP, int CX, bool PM1>
 __device__ __forceinline__ void op_body(unsigned char* smem, const OpCase& k) {
@@ -259,7 +270,7 @@ __device__ __forceinline__ void op_body(unsigned char* smem, const OpCase& k) {
     eo.loss = (k.flags & 8) ? nullptr : k.outf + 3 * d + 1;
     eo.grad = (k.flags & 16) ? nullptr : k.outf + 2 * d;
     epilogue(c, k.mode, d, (float)k.s[1], (float)k.s[2], k.empty != 0, fin, a[0], k.s[0], fin + d, tvec, eo);
-  }
+  } else if constexpr (OP == OP_IPM_ITER) ipm_iter_run<C, PM1>(c, lds, v, k, fin);
 #if defined(CAVE_GPU_CODE)
   else if constexpr (op_is_lite(OP)) {
     // the structures come from the product's own lite_build, on the one-wave context of the one-wave kernels; the solver
@@ -282,6 +293,7 @@ __device__ __forceinline__ void op_body(unsigned char* smem, const OpCase& k) {
       const int hs = p * k.ldh;
       if constexpr (OP == OP_LITE_GATHER) lite_gather(c, L, d, base, a[0], k.s[0], o);
       else if constexpr (OP == OP_LITE_GRAD) lite_gradient(c, L, p, a[0], o);
+      else if constexpr (OP == OP_IPM_LITE) ipm_lite_run(c, lds, v, k, fin, H, wold);
       else if constexpr (OP == OP_LITE_HESS) {
         for (int i = tid; i < hs; i += NT) H[i] = (i % k.ldh) > (i / k.ldh) ? poison_f64() : 0.0;
         for (int i = tid; i < d; i += NT) wold[i] = 0.0f;
@@ -317,7 +329,8 @@ __device__ __forceinline__ void op_body(unsigned char* smem, const OpCase& k) {
 #define CAVE_OP_RB(X, OP) X(OP, CX_W1, true) X(OP, CX_L2, true) X(OP, CX_L4, true)
 #if defined(CAVE_GPU_CODE)
 #define CAVE_OP_LITE_KINDS(X) \
-  X(OP_LITE_GATHER, CX_SOLO, true) X(OP_LITE_GRAD, CX_SOLO, true) X(OP_LITE_HESS, CX_SOLO, true) X(OP_LITE_HESS_IPM, CX_SOLO, true)
+  X(OP_LITE_GATHER, CX_SOLO, true) X(OP_LITE_GRAD, CX_SOLO, true) X(OP_LITE_HESS, CX_SOLO, true) X(OP_LITE_HESS_IPM, CX_SOLO, true) \
+  X(OP_IPM_LITE, CX_SOLO, true)
 #else
 #define CAVE_OP_LITE_KINDS(X)
 #endif
@@ -331,6 +344,7 @@ __device__ __forceinline__ void op_body(unsigned char* smem, const OpCase& k) {
   CAVE_OP_LARGE3(X, OP_BAND_H)                                                                            \
   X(OP_DENSE_H, CX_L2, false) X(OP_DENSE_H, CX_L2, true) X(OP_DENSE_H, CX_L4, false) X(OP_DENSE_H, CX_L4, true) \
   X(OP_EPILOGUE, CX_W1, true) X(OP_EPILOGUE, CX_B4, true) X(OP_EPILOGUE, CX_SOLO, true)                   \
+  X(OP_IPM_ITER, CX_W1, false) X(OP_IPM_ITER, CX_W1, true) X(OP_IPM_ITER, CX_B4, false) X(OP_IPM_ITER, CX_B4, true) \
   CAVE_OP_LITE_KINDS(X)
 
 // the limits the product's dispatch guarantees, and the ones of this harness
@@ -341,6 +355,8 @@ CAVE_HOSTDEV bool op_case_valid(int op, bool pm1, const OpCase& k) {
   if (op == OP_BAND_H && (k.ldh < 1 || k.p < 1)) return false;
   if (op == OP_DENSE_H && (k.p < 1 || k.p > kDenseMaxP)) return false;
   if (op == OP_GRAD_DENSE && !(k.s[0] > 0.0)) return false;
+  if ((op == OP_IPM_ITER || op == OP_IPM_LITE) && (k.n_seq < 0 || k.n_seq > 64 || k.ldh != (k.p | 1) || k.n_out < k.d + 2 * k.p + 3)) return false;
+  if (op == OP_IPM_ITER && k.p > 32) return false;  // PMAX of BlockCtx<4>: the smallest of the contexts
   if (op_is_lite(op) && (k.p < 1 || k.p > kLiteMaxRows || k.d > kLiteMaxD || k.ldh < k.p)) return false;
   return op_lds_bytes(op, pm1, k) <= 160u * 1024u;
 }

@@ -32,7 +32,7 @@ def build(verbose: bool = False) -> str:
     from cave_amd import _lib
 
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    deps = [_SRC, os.path.join(_HERE, "prim_entries.h"), os.path.join(_HERE, "model_entries.h"), os.path.join(_HERE, "op_entries.h")] + [_unit_src(u) for u in _UNITS] + list(_lib._HEADERS)
+    deps = [_SRC, os.path.join(_HERE, "prim_entries.h"), os.path.join(_HERE, "model_entries.h"), os.path.join(_HERE, "op_entries.h"), os.path.join(_HERE, "ipm_entries.h")] + [_unit_src(u) for u in _UNITS] + list(_lib._HEADERS)
     newest = max(os.path.getmtime(p) for p in deps)
     os.makedirs(_OBJ_DIR, exist_ok=True)
     objs = [os.path.join(_OBJ_DIR, u[0] + ".o") for u in _UNITS]
