@@ -12,6 +12,7 @@
 #include "kernels.h"
 #include "cone_entry.h"
 #include "sp_grid.h"
+#include "tight_cones.h"
 #include "tsp_hk.h"
 #include "tsp_hk_wide.h"
 #include "vrp_dp.h"
@@ -475,6 +476,34 @@ int32_t cave_hip_vrp_dp_wide_solve(const float* costs, const float* eval_costs, 
   hipError_t e = launch_vrp_dp_wide((unsigned)grid, (hipStream_t)stream, P);
   if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch vrp_dp_wide kernels", e);
   return CAVE_OK;
+}
+
+// ------------------------------------------------------------------ tight cones of any binary LP (tight_cones.h)
+
+static int32_t tight_cones_entry(bool fill, const cave_lin_system* sys, const cave_lin_system* lazy, const int64_t* lazy_off,
+                                 const float* sol, int64_t N, double tol, int32_t* n_rows, int64_t* n_ent, const int64_t* ent_off,
+                                 int64_t ent_cap, uint32_t* key, float* val, int32_t* status, void* stream) {
+  TightConesParams P;
+  int64_t grid;
+  char msg[kSolverMsg];
+  const int32_t rc = tight_cones_plan(fill, sys, lazy, lazy_off, sol, N, tol, n_rows, n_ent, ent_off, ent_cap, key, val, status, &P,
+                                      &grid, msg);
+  if (rc != CAVE_OK) return fail(rc, msg);
+  if (grid == 0) return CAVE_OK;
+  hipError_t e = launch_tight_cones(fill, (unsigned)grid, (hipStream_t)stream, P);
+  if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch tight_cones_kernel", e);
+  return CAVE_OK;
+}
+
+int32_t cave_hip_tight_cones_count(const cave_lin_system* sys, const cave_lin_system* lazy, const int64_t* lazy_off, const float* sol,
+                                   int64_t N, double tol, int32_t* n_rows, int64_t* n_ent, int32_t* status, void* stream) {
+  return tight_cones_entry(false, sys, lazy, lazy_off, sol, N, tol, n_rows, n_ent, nullptr, 0, nullptr, nullptr, status, stream);
+}
+
+int32_t cave_hip_tight_cones_fill(const cave_lin_system* sys, const cave_lin_system* lazy, const int64_t* lazy_off, const float* sol,
+                                  int64_t N, double tol, const int64_t* ent_off, int64_t ent_cap, uint32_t* key, float* val,
+                                  int32_t* status, void* stream) {
+  return tight_cones_entry(true, sys, lazy, lazy_off, sol, N, tol, nullptr, nullptr, ent_off, ent_cap, key, val, status, stream);
 }
 
 }  // extern "C"

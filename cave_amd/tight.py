@@ -46,6 +46,14 @@ the routes), the cuts from the rule of the reference's callback applied to the s
 workgroup per instance (`vrp_solve_hip`; cave_amd/csrc/vrp_dp.h), bit for bit, and from 13 to 20 nodes with its tables in
 device memory (`vrp_solve_hip_wide`; cave_amd/csrc/vrp_dp_wide.h); `VRPConeDataset(..., device=...)` and
 `vrp_regret(..., device=...)` use the first up to 14 nodes and the second beyond.  The cut loop stays on the host.
+
+Tight cones of any binary LP on the device (`tight_cones_hip`; cave_amd/csrc/tight_cones.h): the rule of
+`_extract_tight_normals` for a batch of vertices of one constraint system in CSR form (`LinSystem`: a model's `getA()`,
+senses and right-hand sides; `tsp_system`, `vrp_system`, `sp_system` are the explicit rows of the three models restated
+here) plus per-instance lazy rows (`cut_rows`: node sets as sparse rows), written directly as SparseCones -- the entries
+`SparseCones.from_ragged` holds for the dense matrices `*_tight_normals` build, without those matrices.
+`TSPConeDataset(..., device=)` and `VRPConeDataset(..., device=, cones="sparse")` use it.  Limits: d <= 65535 columns,
+65535 rows per instance; the cut loops (HiGHS) stay on the host.
 """
 
 from __future__ import annotations
@@ -58,7 +66,8 @@ __all__ = ["sp_solve", "sp_tight_normals", "sp_gen_data", "SPConeDataset", "sp_r
            "tsp_solve", "tsp_dfj_cuts", "tsp_tight_normals", "tsp_gen_data", "TSPConeDataset", "tsp_regret", "tsp_solve_hip",
            "tsp_solve_hip_wide",
            "vrp_solve", "vrp_rcc_cuts", "vrp_tight_normals", "vrp_gen_data", "VRPConeDataset", "vrp_regret", "vrp_solve_hip",
-           "vrp_solve_hip_wide"]
+           "vrp_solve_hip_wide",
+           "LinSystem", "tsp_system", "vrp_system", "sp_system", "cut_rows", "tight_cones_hip"]
 
 
 def sp_solve(cost: np.ndarray, h: int, w: int):
@@ -444,12 +453,31 @@ def tsp_gen_data(num_data: int, num_feat: int, n: int, deg: int = 4, noise_width
 
 
 class TSPConeDataset:
-    """`optDatasetConstrs` (src/dataset.py:26-130) for the DFJ TSP model without Gurobi."""
+    """`optDatasetConstrs` (src/dataset.py:26-130) for the DFJ TSP model without Gurobi.
 
-    def __init__(self, feats: np.ndarray, costs: np.ndarray, n: int):
+    With `device`: the cut loop runs on the host as always and its vertex is kept; the tight cones are written on the
+    device by `tight_cones_hip` from the degree rows (`tsp_system`) and the cuts as sparse lazy rows (`cut_rows`).  There
+    is no dense `ctrs` list: feats, costs, sols and objs live on the device, `.cones` is the SparseCones of the whole set
+    and item i carries its one-instance slice (views, no copy), as `SPConeDataset(..., device=)` does."""
+
+    def __init__(self, feats: np.ndarray, costs: np.ndarray, n: int, device=None):
         import torch
 
         self.n = n
+        self.cones = None
+        if device is not None:
+            device = torch.device(device)
+            sols, objs, cuts = [], [], []
+            for c in costs:
+                s, o, k = tsp_dfj_cuts(c, n)
+                sols.append(s)
+                objs.append(o)
+                cuts.append(k)
+            sols = torch.as_tensor(np.stack(sols), dtype=torch.float32).to(device)
+            cones, n_rows = _tight_cones_call(tsp_system(n), sols, cut_rows(n, cuts), 1e-5)
+            _device_cone_items(self, device, feats, costs, sols, objs, cones)
+            self.tight_cuts = [int(v) - 2 * n - sols.shape[1] for v in n_rows.tolist()]
+            return
         sols, objs, ctrs, ncuts = [], [], [], []
         for c in costs:
             s, o, cuts = tsp_dfj_cuts(c, n)
@@ -469,6 +497,8 @@ class TSPConeDataset:
         return len(self.feats)
 
     def __getitem__(self, i: int):
+        if self.cones is not None:
+            return _device_cone_item(self, i)
         return self.feats[i], self.costs[i], self.sols[i], self.objs[i], self.ctrs[i]
 
 
@@ -782,14 +812,34 @@ class VRPConeDataset:
     from 15 to 20, beyond the host solver's reach), cuts from the cutting loop
     (`vrp_rcc_cuts`, host), rows those tight at the dynamic program's vertex -- a cut is a valid inequality, so it is a
     valid generator at any vertex where it is tight.  An infeasible instance raises ValueError, as the reference does
-    without `skip_infeas`."""
+    without `skip_infeas`.
 
-    def __init__(self, feats: np.ndarray, costs: np.ndarray, n: int, demands, capacity: float, num_vehicle: int, device=None):
+    `cones="sparse"` (needs `device`): the device solver's vertices stay on the device and the tight cones are written
+    there by `tight_cones_hip` from `vrp_system` and the cuts as sparse lazy rows (`cut_rows`): no dense `ctrs` list,
+    feats, costs, sols and objs on the device, `.cones` the SparseCones of the whole set, item i its one-instance slice.
+    The default, `cones="dense"`, is what it always was."""
+
+    def __init__(self, feats: np.ndarray, costs: np.ndarray, n: int, demands, capacity: float, num_vehicle: int, device=None,
+                 cones: str = "dense"):
         import torch
 
         self.n, self.capacity, self.num_vehicle = n, float(capacity), int(num_vehicle)
         self.demands = np.asarray(demands, dtype=np.float32).reshape(-1)
         costs = np.asarray(costs, dtype=np.float32)
+        if cones not in ("dense", "sparse"):
+            raise ValueError(f"VRPConeDataset: cones must be 'dense' or 'sparse', not {cones!r}")
+        self.cones = None
+        if cones == "sparse":
+            if device is None:
+                raise ValueError("VRPConeDataset: cones='sparse' writes the cones on the device and needs `device`")
+            device = torch.device(device)
+            s, o, _ = _vrp_solve_hip_for(n)(torch.as_tensor(costs).to(device), n, self.demands, capacity, num_vehicle)
+            cuts = [vrp_rcc_cuts(c, n, self.demands, capacity, num_vehicle)[2] for c in costs]
+            made, n_rows = _tight_cones_call(vrp_system(n, num_vehicle), s, cut_rows(n, cuts), 1e-5)
+            _device_cone_items(self, device, feats, costs, s, o.cpu().numpy(), made)
+            depot = ((s[:, :n - 1].to(torch.float64).sum(1) - 2.0 * self.num_vehicle).abs() < 1e-5).to(torch.int32)  # its row is tight
+            self.tight_cuts = [int(v) for v in (n_rows - depot - 2 * (n - 1) - s.shape[1]).tolist()]
+            return
         if device is not None:
             s, o, _ = _vrp_solve_hip_for(n)(torch.as_tensor(costs).to(torch.device(device)), n, self.demands, capacity, num_vehicle)
             sols, objs = list(s.cpu().numpy()), [[float(v)] for v in o.cpu().numpy()]
@@ -816,6 +866,8 @@ class VRPConeDataset:
         return len(self.feats)
 
     def __getitem__(self, i: int):
+        if self.cones is not None:
+            return _device_cone_item(self, i)
         return self.feats[i], self.costs[i], self.sols[i], self.objs[i], self.ctrs[i]
 
 
@@ -836,3 +888,244 @@ def vrp_regret(pred_costs: np.ndarray, true_costs: np.ndarray, true_objs: np.nda
         s, _, _ = vrp_solve(cp, n, demands, capacity, num_vehicle)
         loss += float(c @ s) - float(np.asarray(z).reshape(-1)[0])
     return loss / float(np.abs(true_objs).sum() + 1e-7)
+
+
+# ------------------------------------------------------------------ tight cones of any binary LP, on the device
+
+_SENSES = {"<": 0, "<=": 0, "L": 0, 0: 0, ">": 1, ">=": 1, "G": 1, 1: 1, "=": 2, "==": 2, "E": 2, 2: 2}
+MAX_DIM = 65535  # columns of a system and rows of a cone (16 bits each in a key)
+
+
+class LinSystem:
+    """A constraint system `A x (sense) rhs` in the CSR form the tight-cone kernels read (`struct cave_lin_system`,
+    include/cave_hip.h): what a Gurobi model hands out as `getA()` restricted to the cost columns, `Sense` and `RHS`.
+
+    `A`: a scipy.sparse matrix or a dense (R, d) array; `senses`: one of '<', '>', '=' per row (Gurobi's characters; also
+    '<=', '>=', '==' and the codes 0, 1, 2) or one for all rows; `rhs`: a number per row or one for all.  Canonicalised on
+    the host once: coefficients as float32, columns sorted within a row, repeated entries summed, explicit zeros dropped.
+    `to(device)` moves the five arrays there once (cached per device)."""
+
+    def __init__(self, A, senses, rhs):
+        from scipy.sparse import csr_matrix, issparse
+
+        if issparse(A):
+            M = csr_matrix(A, dtype=np.float64, copy=True)
+        else:
+            a = np.asarray(A, dtype=np.float64)
+            if a.ndim != 2:
+                raise ValueError("LinSystem: A must be a scipy.sparse matrix or a dense (R, d) array")
+            M = csr_matrix(a)
+        R, d = M.shape
+        if not 1 <= d <= MAX_DIM:
+            raise ValueError(f"LinSystem: need 1 <= d <= {MAX_DIM} columns, not {d}")
+        M.sum_duplicates()
+        M.data = M.data.astype(np.float32).astype(np.float64)  # (a value that underflows in float32 is an explicit zero)
+        M.eliminate_zeros()
+        M.sort_indices()
+        if not np.isfinite(M.data).all():
+            raise ValueError("LinSystem: a coefficient is not finite")
+        if isinstance(senses, (str, bytes, int, np.integer)):
+            senses = [senses] * R
+        senses = [s.decode() if isinstance(s, bytes) else (int(s) if isinstance(s, np.integer) else s) for s in senses]
+        if len(senses) != R:
+            raise ValueError(f"LinSystem: {R} rows, {len(senses)} senses")
+        for s in senses:
+            if not isinstance(s, (str, int)) or s not in _SENSES:
+                raise ValueError(f"Invalid constraint sense {s!r}.")  # (the reference's message, src/dataset.py:176)
+        rhs = np.asarray(rhs, dtype=np.float64)
+        rhs = np.full(R, float(rhs)) if rhs.ndim == 0 else rhs.reshape(-1).copy()
+        if len(rhs) != R:
+            raise ValueError(f"LinSystem: {R} rows, {len(rhs)} right-hand sides")
+        if not np.isfinite(rhs).all():
+            raise ValueError("LinSystem: a right-hand side is not finite")
+        self.R, self.d = int(R), int(d)
+        self.row_off = M.indptr.astype(np.int64)
+        self.col = M.indices.astype(np.int32)
+        self.coef = M.data.astype(np.float32)
+        self.sense = np.array([_SENSES[s] for s in senses], dtype=np.int8)
+        self.rhs = rhs
+        self._dev: dict = {}
+
+    @property
+    def nnz(self) -> int:
+        return int(self.col.size)
+
+    def dense(self) -> np.ndarray:
+        """the (R, d) float32 matrix (tests, small systems)"""
+        a = np.zeros((self.R, self.d), dtype=np.float32)
+        a[np.repeat(np.arange(self.R), np.diff(self.row_off)), self.col] = self.coef
+        return a
+
+    def to(self, device):
+        """-> (struct cave_lin_system over this system's arrays on `device`, the tensors it points to); moved once"""
+        import torch
+
+        from . import _lib
+
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        hit = self._dev.get(device)
+        if hit is None:
+            t = [torch.from_numpy(a).to(device) for a in (self.row_off, self.col, self.coef, self.sense, self.rhs)]
+            c = _lib.LinSystemC(R=self.R, Z=self.nnz, d=self.d, reserved=0, row_off=t[0].data_ptr(), col=t[1].data_ptr(),
+                                coef=t[2].data_ptr(), sense=t[3].data_ptr(), rhs=t[4].data_ptr())
+            hit = self._dev[device] = (c, t)
+        return hit
+
+
+def _edge_rows(n: int):
+    """the node-edge incidence of the complete graph on n nodes in CSR form: row v holds its n-1 edges, ascending"""
+    from scipy.sparse import csr_matrix
+
+    from .synth import tsp_edges
+
+    edges = tsp_edges(n)
+    d = len(edges)
+    return csr_matrix((np.ones(2 * d), (np.r_[edges[:, 0], edges[:, 1]], np.r_[np.arange(d), np.arange(d)])), shape=(n, d))
+
+
+def tsp_system(n: int) -> LinSystem:
+    """The explicit rows of the DFJ model (src/model/tsp.py:54-60): every node's degree == 2."""
+    return LinSystem(_edge_rows(int(n)), "=", 2.0)
+
+
+def vrp_system(n: int, num_vehicle: int) -> LinSystem:
+    """The explicit rows of `vrpModel` (src/model/vrp.py): depot degree <= 2K, every customer's degree == 2."""
+    n = int(n)
+    return LinSystem(_edge_rows(n), ["<"] + ["="] * (n - 1), [2.0 * int(num_vehicle)] + [2.0] * (n - 1))
+
+
+def sp_system(h: int, w: int) -> LinSystem:
+    """The explicit rows of the grid shortest-path model: flow conservation per node (+1 on the arcs entering it, -1 on
+    those leaving it) == -1 at the source, +1 at the sink, 0 elsewhere."""
+    from scipy.sparse import csr_matrix
+
+    arcs = sp_arcs(h, w)
+    d, nn = len(arcs), h * w
+    A = csr_matrix((np.r_[np.ones(d), -np.ones(d)], (np.r_[arcs[:, 1], arcs[:, 0]], np.r_[np.arange(d), np.arange(d)])), shape=(nn, d))
+    rhs = np.zeros(nn)
+    rhs[0], rhs[nn - 1] = -1.0, 1.0
+    return LinSystem(A, "=", rhs)
+
+
+def cut_rows(n: int, cuts_per_instance, sense="<"):
+    """Lazy rows from node sets, built sparse: per instance a list of cuts, a cut being a node list S -- the subtour row
+    x(E(S)) <= |S| - 1 of `tsp_dfj_cuts` -- or a pair (S, rhs) as `vrp_rcc_cuts` returns.  -> (LinSystem of all the rows
+    in list order, lazy_off (N+1,) int64): what `tight_cones_hip(..., lazy=)` takes.  Edge columns as everywhere here:
+    lexicographic (i < j)."""
+    from scipy.sparse import csr_matrix
+
+    n = int(n)
+    d = n * (n - 1) // 2
+    cols, ptr, rhs, off = [], [0], [], [0]
+    for cuts in cuts_per_instance:
+        for cut in cuts:
+            pair = isinstance(cut, tuple) and len(cut) == 2 and not np.isscalar(cut[0])
+            comp = np.unique(np.asarray(cut[0] if pair else cut, dtype=np.int64))
+            if comp.size and (comp[0] < 0 or comp[-1] >= n):
+                raise ValueError(f"cut_rows: a node outside 0..{n - 1}")
+            a, b = np.triu_indices(comp.size, 1)
+            a, b = comp[a], comp[b]
+            cols.append(a * n - a * (a + 1) // 2 + b - a - 1)  # ascending: (a, b) runs in lexicographic order
+            ptr.append(ptr[-1] + a.size)
+            rhs.append(float(cut[1]) if pair else comp.size - 1.0)
+        off.append(len(rhs))
+    cols = np.concatenate(cols) if cols else np.zeros(0, np.int64)
+    A = csr_matrix((np.ones(cols.size), cols, np.asarray(ptr, dtype=np.int64)), shape=(len(rhs), d))
+    return LinSystem(A, sense, np.asarray(rhs, dtype=np.float64)), np.asarray(off, dtype=np.int64)
+
+
+def _tight_cones_call(system: LinSystem, sols, lazy, tol: float):
+    """count pass, prefix sums, one host read, fill pass -> (SparseCones on the device, n_rows (N,) int32 there)"""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+    from .sparse import SparseCones
+
+    lib = _lib.load()  # (no device: ImportError before any check of the arguments)
+    if not isinstance(system, LinSystem):
+        raise TypeError("tight_cones_hip: system must be a LinSystem")
+    if not (isinstance(sols, torch.Tensor) and sols.is_cuda and sols.dtype == torch.float32 and sols.dim() == 2):
+        raise ValueError("tight_cones_hip: sols must be a (N, d) float32 tensor on the device")
+    if sols.shape[1] != system.d:
+        raise ValueError(f"tight_cones_hip: the system has {system.d} columns, sols has {sols.shape[1]}")
+    tol = float(tol)
+    if not (np.isfinite(tol) and tol >= 0):
+        raise ValueError("tight_cones_hip: tol must be finite and >= 0")
+    sols = sols.contiguous()
+    N, dev = sols.shape[0], sols.device
+    sys_c, _keep = system.to(dev)
+    lazy_c, lazy_off = None, None
+    if lazy is not None:
+        lz, off = lazy
+        off = off if isinstance(off, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(off, dtype=np.int64))
+        if not isinstance(lz, LinSystem) or lz.d != system.d:
+            raise ValueError("tight_cones_hip: lazy must be (LinSystem over the same columns, lazy_off)")
+        if off.numel() != N + 1:
+            raise ValueError(f"tight_cones_hip: lazy_off must hold N + 1 = {N + 1} offsets")
+        lazy_c, _keep_lazy = lz.to(dev)
+        lazy_off = off.to(device=dev, dtype=torch.int64).contiguous()
+    n_rows = torch.empty(N, dtype=torch.int32, device=dev)
+    n_ent = torch.empty(N, dtype=torch.int64, device=dev)
+    status = torch.empty(N, dtype=torch.int32, device=dev)
+    ent_off = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+    p = _lib.ptr
+    ref = lambda c: None if c is None else C.byref(c)  # noqa: E731
+    with torch.cuda.device(dev):
+        stream = _lib.current_stream()
+        _lib.check(lib.cave_hip_tight_cones_count(ref(sys_c), ref(lazy_c), p(lazy_off), p(sols), N, tol, p(n_rows), p(n_ent),
+                                                  p(status), stream), "cave_hip_tight_cones_count")
+        if N:
+            torch.cumsum(n_ent, 0, out=ent_off[1:])
+            total, m_max, failed = (int(v) for v in torch.stack([ent_off[-1], n_rows.max().to(torch.int64),
+                                                                  (status != _lib.ST_OK).any().to(torch.int64)]).tolist())
+        else:
+            total, m_max, failed = 0, 0, 0
+        if failed:
+            bad = int(torch.nonzero(status != _lib.ST_OK)[0])
+            if int(status[bad]) == _lib.ST_TOO_LARGE:
+                raise ValueError(f"tight_cones_hip: instance {bad} has more than {MAX_DIM} tight rows")
+            raise ValueError(f"tight_cones_hip: instance {bad} has a non-finite solution value or a lazy row that breaks the "
+                             "contract of cave_lin_system (or the shared system does)")
+        key = torch.empty(total, dtype=torch.int32, device=dev)
+        val = torch.empty(total, dtype=torch.float32, device=dev)
+        _lib.check(lib.cave_hip_tight_cones_fill(ref(sys_c), ref(lazy_c), p(lazy_off), p(sols), N, tol, p(ent_off), total,
+                                                 p(key), p(val), None, stream), "cave_hip_tight_cones_fill")
+    return SparseCones(m_max, system.d, ent_off, key, val), n_rows
+
+
+def tight_cones_hip(system: LinSystem, sols, lazy=None, tol: float = 1e-5):
+    """`_extract_tight_normals` (src/dataset.py:147-215) for a batch of vertices on the device: sols (N, d) float32 there,
+    `system` the model's explicit rows, `lazy` None or `(LinSystem, lazy_off)` -- the rows lazy_off[b]:lazy_off[b+1] are
+    instance b's lazy constraints (`cut_rows` builds the pair from node sets) -> the SparseCones
+    `SparseCones.from_ragged([that function's matrix per instance])` holds, on the device, without the dense matrix:
+    count pass, `torch.cumsum`, one host read (the total and the largest row count), fill pass.  Limits: d <= 65535
+    columns, 65535 rows per instance.  The first instance the device rejects raises ValueError."""
+    return _tight_cones_call(system, sols, lazy, tol)[0]
+
+
+def _device_cone_items(self, device, feats, costs, sols, objs, cones):
+    """what the `device=` forms of the TSP and CVRP data sets keep: everything on the device, the whole set's cones, and
+    the offsets that slice an item's cone out of them (instances differ in size)"""
+    import torch
+
+    self.feats = torch.as_tensor(feats, dtype=torch.float32).to(device)
+    self.costs = torch.as_tensor(costs, dtype=torch.float32).to(device)
+    self.sols = sols
+    self.objs = torch.as_tensor(np.asarray(objs), dtype=torch.float32).reshape(-1, 1).to(device)
+    self.cones = cones
+    self._ent = [int(v) for v in cones.ent_off.tolist()]
+    z = torch.zeros(len(self._ent) - 1, dtype=torch.int64, device=device)
+    self._off2 = torch.stack([z, cones.ent_off[1:] - cones.ent_off[:-1]], dim=1)  # row i: the ent_off of item i's cone
+
+
+def _device_cone_item(self, i: int):
+    from .sparse import SparseCones
+
+    i = int(i) % len(self)
+    lo, hi = self._ent[i], self._ent[i + 1]
+    cone = SparseCones(self.cones.m_max, self.cones.d, self._off2[i], self.cones.key[lo:hi], self.cones.val[lo:hi])
+    return self.feats[i], self.costs[i], self.sols[i], self.objs[i], cone

@@ -16,6 +16,7 @@ reference's CVRP model (2-degree rows, rounded-capacity cuts), solved by the dyn
     python examples/train_sp_cave.py --problem tsp --nodes 12 --packed --device-regret  # the regret's Held-Karp solves run on the device
     python examples/train_sp_cave.py --problem tsp --nodes 20 --num-data 64 --packed --device-regret  # TSP-20: above 14 nodes only the device solves exactly
     python examples/train_sp_cave.py --problem vrp --nodes 10 --capacity 30 --vehicles 3 --packed --device-regret --device-data  # CVRP: solved on the device
+    python examples/train_sp_cave.py --problem tsp --nodes 10 --sparse --device-cones  # TSP: the tight cones are written on the device, no dense matrix
     python examples/train_sp_cave.py --problem vrp --nodes 16 --capacity 40 --vehicles 3 --num-data 32 --packed --device-regret --device-data  # CVRP-15: above 14 nodes only the device solves exactly
 """
 
@@ -75,7 +76,14 @@ def main(argv=None):
                     help="evaluate the regret on the device (tsp_regret / vrp_regret / sp_regret(..., device=)): one launch "
                          "solves every prediction and prices it, only the scalar comes back; the dataset and the training "
                          "loop are untouched")
+    ap.add_argument("--device-cones", action="store_true",
+                    help="(TSP / CVRP, with --sparse or --packed) write the data set's tight cones on the device, on the sparse "
+                         "wire format (TSPConeDataset(..., device=), VRPConeDataset(..., device=, cones='sparse'): "
+                         "tight.tight_cones_hip): no dense cone is ever made; the cut loop stays on the host")
     args = ap.parse_args(argv)
+    if args.device_cones and (args.problem == "sp" or not (args.packed or args.sparse)):
+        ap.error("--device-cones is for --problem tsp and --problem vrp, where it needs --sparse or --packed (there are no dense "
+                 "cones); the shortest path has --device-data")
     if args.device_data and (args.problem == "tsp" or (args.problem == "sp" and not (args.packed or args.sparse))):
         ap.error("--device-data is for the shortest-path problem, where it needs --packed or --sparse (there are no dense "
                  "cones), and for the CVRP")
@@ -100,12 +108,13 @@ def main(argv=None):
     h, w = args.grid
     if args.problem == "tsp":
         feats, costs = tsp_gen_data(args.num_data, args.num_feat, args.nodes, deg=4, noise_width=0.5, seed=42)
-        dataset = TSPConeDataset(feats, costs, args.nodes)
+        dataset = TSPConeDataset(feats, costs, args.nodes, device="cuda" if args.device_cones else None)
         print(f"TSP-{args.nodes}: {len(dataset)} instances, {sum(dataset.tight_cuts)} tight subtour cuts in all")
     elif args.problem == "vrp":
         feats, costs, demands = vrp_gen_data(args.num_data, args.num_feat, args.nodes, deg=4, noise_width=0.5, seed=42)
         dataset = VRPConeDataset(feats, costs, args.nodes, demands, args.capacity, args.vehicles,
-                                 device="cuda" if args.device_data else None)
+                                 device="cuda" if args.device_data or args.device_cones else None,
+                                 cones="sparse" if args.device_cones else "dense")
         print(f"CVRP-{args.nodes - 1} (capacity {args.capacity:g}, {args.vehicles} vehicles): {len(dataset)} instances, "
               f"{sum(dataset.tight_cuts)} tight rounded-capacity cuts in all")
     else:
@@ -133,8 +142,9 @@ def main(argv=None):
         cave = innerConeAlignedCosine(_Model(), solver="hip", solve_ratio=0.3, inner_ratio=0.2, seed=0, solver_kwargs=kw or None)
 
     # --sparse: what a dataset built from a solver's sparse constraint matrix would keep -- one SparseCones per instance
-    if sp_device:
-        sparse_ctrs = dataset.cones   # already on the device, straight from the solve kernel
+    dev_cones = sp_device or args.device_cones
+    if dev_cones:
+        sparse_ctrs = dataset.cones   # already on the device, straight from the solve kernel / the tight-cone kernels
     else:
         sparse_ctrs = SparseCones.from_ragged(dataset.ctrs) if args.sparse else None
     if args.packed:
@@ -149,7 +159,7 @@ def main(argv=None):
         x, c = dataset.feats[idx.to(dataset.feats.device)], dataset.costs[idx.to(dataset.costs.device)]
         if args.packed:
             return x, c, idx
-        if sp_device:
+        if dev_cones:
             return x, c, sparse_ctrs[idx]   # one gather on the device
         if args.sparse:
             return collate_sparse([(x[j], c[j], sparse_ctrs[i]) for j, i in enumerate(batch)])
@@ -221,10 +231,11 @@ def main(argv=None):
                 return sp_regret(cp, dataset.costs, dataset.objs[:, 0], h, w, device=dev)
         with torch.no_grad():
             cp = reg(dataset.feats.to(dev)).cpu().numpy()
-        if args.problem == "tsp":
-            return tsp_regret(cp, dataset.costs.numpy(), dataset.objs.numpy()[:, 0], args.nodes)
+        if args.problem == "tsp":  # (.cpu(): with --device-cones the data set lives on the device)
+            return tsp_regret(cp, dataset.costs.cpu().numpy(), dataset.objs.cpu().numpy()[:, 0], args.nodes)
         if args.problem == "vrp":
-            return vrp_regret(cp, dataset.costs.numpy(), dataset.objs.numpy()[:, 0], args.nodes, demands, args.capacity, args.vehicles)
+            return vrp_regret(cp, dataset.costs.cpu().numpy(), dataset.objs.cpu().numpy()[:, 0], args.nodes, demands, args.capacity,
+                              args.vehicles)
         return sp_regret(cp, dataset.costs.numpy(), dataset.objs.numpy()[:, 0], h, w)
 
     hist = [(0, float("nan"), regret())]

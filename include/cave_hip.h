@@ -571,6 +571,61 @@ int32_t cave_hip_vrp_dp_wide_solve(const float* costs, const float* eval_costs, 
                                    int64_t K, int64_t N, int64_t n, float* sol, double* obj, double* eval,
                                    int32_t* routes, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ tight cones of any binary LP (additive to v10)
+ * The reference's extraction rule (`_extract_tight_normals`, src/dataset.py:147-215) for N vertices of one constraint
+ * system, written directly on the sparse wire format (cave_sparse_cones): what cave_hip_sp_grid_solve's key / val do for
+ * the grid's node-arc matrix, for any matrix.  A system is R rows over d columns in CSR form; every array a device
+ * pointer, caller-owned, read-only:
+ *   row_off [R+1] int64   0 <= row_off[r] <= row_off[r+1] <= Z
+ *   col     [Z]   int32   0 <= col < d, strictly increasing within a row
+ *   coef    [Z]   fp32    non-zero and finite
+ *   sense   [R]   int8    0 `<=`, 1 `>=`, 2 `==`
+ *   rhs     [R]   fp64    finite
+ * `sys` is shared by the batch.  `lazy` (or NULL) is a second system over the same d whose rows lazy_off[b] ..
+ * lazy_off[b+1] (lazy_off [N+1] int64, 0 <= lazy_off[b] <= lazy_off[b+1] <= lazy->R) belong to instance b alone.
+ * sol [N, d] fp32 holds the vertices; tol (fp64, finite, >= 0) is the reference's `tol`.
+ * A row is tight when |rhs - sum_j (double)coef_j (double)sol_j| < tol, products and sum in fp64 (the order of the
+ * additions is not fixed).  Per instance the rows are numbered from 0 in this order, and the entries come out in strictly
+ * increasing key = (row << 16) | col:
+ *   1 the tight `<=` rows of sys, in row order, as they are     2 the tight `>=` rows, negated
+ *   3 the tight `==` rows, as they are                          4 the same `==` rows, negated
+ *   5 the instance's tight lazy rows in list order, each oriented: `>=` negated, `==` the row and then its negation
+ *   6 -e_k for every k with (double)sol_k <= tol, ascending     7 +e_k for every k with (double)sol_k >= 1 - tol, not in 6
+ * A tight row without entries takes a row number and writes nothing (the zero row the reference would emit).
+ * Two passes, because the entry count differs per instance:
+ *   cave_hip_tight_cones_count  writes n_rows [N] int32 (a cave_sparse_cones' m_max is their maximum), n_ent [N] int64
+ *                               and status [N] (or NULL)
+ *   cave_hip_tight_cones_fill   takes ent_off [N+1] int64, the caller's exclusive scan of n_ent, and writes key / val
+ *                               [ent_cap] (ent_cap >= ent_off[N]); status [N] or NULL
+ * Per-instance status: CAVE_ST_BAD_INPUT for a non-finite sol value, a lazy_off window or a lazy row of that instance
+ * that breaks the contract above (the other instances are unaffected), and -- for every instance alike -- a sys that
+ * breaks it; CAVE_ST_TOO_LARGE for more than 65535 rows.  A failed instance counts 0 rows and 0 entries, and the fill
+ * pass writes nothing for it; the fill pass also writes nothing, and reports CAVE_ST_BAD_INPUT, for an instance whose
+ * window ent_off[b] .. ent_off[b+1] is not the size the count pass reports or does not lie in [0, ent_cap].  Every index
+ * read from an input is checked before it is used: nothing is read or written out of range.  One wave per instance, no
+ * workspace, no state between calls; results do not depend on the batch or the launch.  N == 0: nothing to do, CAVE_OK.
+ * CAVE_E_INVALID before any launch: sys NULL; d outside 1..65535; lazy->d != sys->d; a negative R, Z, N or ent_cap; tol
+ * not finite or < 0; lazy rows (lazy->R > 0) without lazy_off; with N > 0 a null or misaligned array (those of a system
+ * with R > 0 -- col / coef with Z > 0 --, sol, n_rows, n_ent, ent_off, key / val with ent_cap > 0; a given lazy_off). */
+typedef struct cave_lin_system {
+  int64_t R;       /* rows */
+  int64_t Z;       /* entries: row_off[R] */
+  int32_t d;       /* columns, 1..65535 */
+  int32_t reserved;
+  const int64_t* row_off;
+  const int32_t* col;
+  const float* coef;
+  const int8_t* sense;
+  const double* rhs;
+} cave_lin_system;
+
+int32_t cave_hip_tight_cones_count(const cave_lin_system* sys, const cave_lin_system* lazy, const int64_t* lazy_off,
+                                   const float* sol, int64_t N, double tol, int32_t* n_rows, int64_t* n_ent, int32_t* status,
+                                   void* stream);
+int32_t cave_hip_tight_cones_fill(const cave_lin_system* sys, const cave_lin_system* lazy, const int64_t* lazy_off,
+                                  const float* sol, int64_t N, double tol, const int64_t* ent_off, int64_t ent_cap,
+                                  uint32_t* key, float* val, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
