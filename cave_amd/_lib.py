@@ -18,12 +18,12 @@ _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.path.join(_HERE, "libcave_hip.so")
 _CSRC = os.path.join(_HERE, "csrc")
 _HEADERS = [os.path.join(_CSRC, n) for n in ("kernels.h", "cone_common.h", "cone_core.h", "cone_band.h", "cone_dense.h", "cone_rb.h", "cone_instance.h", "cone_step.h", "cone_entry.h",
-                                             "wave_prims.h", "ctx_wave.h", "ctx_block.h", "solver_entry.h", "sp_grid.h", "tight_cones.h", "tsp_hk.h", "vrp_dp.h", "tsp_hk_wide.h", "vrp_dp_wide.h")] + \
+                                             "wave_prims.h", "ctx_wave.h", "ctx_block.h", "solver_entry.h", "sp_grid.h", "tight_cones.h", "tsp_hk.h", "vrp_dp.h", "tsp_hk_wide.h", "vrp_dp_wide.h", "apgd.h")] + \
     [os.path.join(_ROOT, "include", "cave_hip.h")]
 # translation units: the C ABI (host code) + one file per kernel shape (cave_amd/csrc/kernels.h)
 _UNITS = ["cave_hip"] + [f"k_{op}_w{w}" for op in ("dense", "pack", "packed") for w in (1, 2, 4, 8)] + \
     ["k_large_dense", "k_large_pack", "k_large_packed_w1", "k_large_packed_w2", "k_large_packed_w4", "k_step",
-     "k_step_warm", "k_step_sparse", "k_step_sparse_warm", "k_step_ipm", "k_step_sparse_ipm", "k_pack_sparse_w2", "k_pack_sparse_w4", "k_pack_sparse_w8", "k_large_pack_sparse", "k_sp_grid", "k_tight_cones", "k_tsp_hk", "k_vrp_dp", "k_tsp_hk_wide", "k_vrp_dp_wide"]
+     "k_step_warm", "k_step_sparse", "k_step_sparse_warm", "k_step_ipm", "k_step_sparse_ipm", "k_pack_sparse_w2", "k_pack_sparse_w4", "k_pack_sparse_w8", "k_large_pack_sparse", "k_sp_grid", "k_tight_cones", "k_tsp_hk", "k_vrp_dp", "k_tsp_hk_wide", "k_vrp_dp_wide", "k_apgd_w1", "k_apgd_w4"]
 _SOURCES = [os.path.join(_CSRC, u + ".hip") for u in _UNITS] + _HEADERS
 _OBJ_DIR = os.path.join(_CSRC, "build")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
@@ -48,6 +48,7 @@ ABI_SYMBOLS = (
     "cave_hip_tsp_hk_wide_slot_bytes", "cave_hip_tsp_hk_wide_workspace_bytes", "cave_hip_tsp_hk_wide_solve",
     "cave_hip_vrp_dp_wide_slot_bytes", "cave_hip_vrp_dp_wide_workspace_bytes", "cave_hip_vrp_dp_wide_solve",
     "cave_hip_tight_cones_count", "cave_hip_tight_cones_fill",
+    "cave_hip_apgd_lds_bytes", "cave_hip_cone_apgd", "cave_hip_cone_apgd_sparse",
 )
 
 
@@ -257,6 +258,11 @@ def load_library() -> C.CDLL:
     lib.cave_hip_tight_cones_fill.argtypes = [C.POINTER(LinSystemC), C.POINTER(LinSystemC), vp, vp, i64, C.c_double, vp, i64, vp, vp,
                                               vp, vp]
     lib.cave_hip_tight_cones_count.restype = lib.cave_hip_tight_cones_fill.restype = i32
+    lib.cave_hip_apgd_lds_bytes.argtypes = [i64, i64, i64]
+    lib.cave_hip_cone_apgd.argtypes = [vp, vp, i64, i64, i64, i32, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.cave_hip_cone_apgd_sparse.argtypes = [C.POINTER(SparseConesC), vp, i32, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                              vp, vp, vp, vp]
+    lib.cave_hip_apgd_lds_bytes.restype = lib.cave_hip_cone_apgd.restype = lib.cave_hip_cone_apgd_sparse.restype = i32
     _lib = lib
     return lib
 

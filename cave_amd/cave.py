@@ -44,10 +44,30 @@ def _packed_kwargs(kwargs: dict) -> dict:
     return {k: v for k, v in kwargs.items() if k in ("max_iter", "check")}
 
 
+_APGD_KEYS = ("max_iters", "tol_grad", "check_frequency", "power_iter")  # the reference's names (src/qpsolver.py:11-18)
+
+
 def _op_kwargs(kwargs: dict) -> dict:
     """solver_kwargs minus the keys the loss modules consume themselves ('inner': the kind of interior point,
-    'warm_start': the multiplier cache)."""
-    return {k: v for k, v in kwargs.items() if k not in ("inner", "warm_start")}
+    'warm_start': the multiplier cache; on the APGD arm of innerConeAlignedCosine -- '_apgd', set by its
+    _solver_kwargs_for_call -- also the projector's own keys, which no other entry takes)."""
+    drop = ("inner", "warm_start", "_apgd") + (_APGD_KEYS if kwargs.get("_apgd") else ())
+    return {k: v for k, v in kwargs.items() if k not in drop}
+
+
+def _apgd_op(tight_ctrs, pred_cost, mode, sign, kwargs: dict, check: bool, outputs):
+    """The inner='apgd' arm: the reference's chunked APGD loop on the device (qpsolver._apgd_chunks) for a dense tensor or
+    a SparseCones; a PreparedCones is unwrapped to the batch it keeps.  A store cannot serve: it holds reduced cones."""
+    from .qpsolver import _apgd_chunks
+
+    if isinstance(tight_ctrs, PackedBatch):
+        raise ValueError("solver_kwargs['inner'] = 'apgd' iterates on the rows of the wire format as they are; a PackedBatch's "
+                         "store holds reduced cones (pairs merged, unit rows eliminated). Pass the dense tensor or a SparseCones.")
+    if isinstance(tight_ctrs, PreparedCones):
+        tight_ctrs = tight_ctrs.ctrs
+    out, _, _ = _apgd_chunks(tight_ctrs, pred_cost, mode, sign, kwargs.get("max_iters", 200), kwargs.get("tol_grad"),
+                             kwargs.get("check_frequency", 200), kwargs.get("power_iter", 8), check, outputs)
+    return out
 
 
 _WARM_MODES = (_lib.MODE_PROJECT, _lib.MODE_EXACT, _lib.MODE_INNER)  # (HEURISTIC / AVG solve nothing; IPM runs cold)
@@ -145,6 +165,8 @@ class _ConeLossFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred_cost, tight_ctrs, mode, sign, inner_ratio, kwargs):
+        if kwargs.get("_apgd") and mode == _lib.MODE_EXACT:
+            return _ConeLossFunction._forward_apgd(ctx, pred_cost, tight_ctrs, mode, sign, kwargs)
         warm = kwargs.get("warm_start")  # (a WarmCache: solver_kwargs={"warm_start": ...}, see _solver_kwargs_for_call)
         warm = warm if isinstance(warm, WarmCache) else None
         kwargs = _op_kwargs(kwargs)
@@ -216,6 +238,32 @@ class _ConeLossFunction(torch.autograd.Function):
         return loss.to(device=pred_cost.device, dtype=pred_cost.dtype)
 
     @staticmethod
+    def _forward_apgd(ctx, pred_cost, tight_ctrs, mode, sign, kwargs):
+        """inner='apgd': the target is the normalised truncated APGD iterate (src/cave.py:213-214 with solver='apgd');
+        always cold.  `check`: True / False / 'lazy' as on the other routes (a dense shape whose entry capacity has not
+        settled yet runs its first lazy call strict)."""
+        from . import qpsolver
+
+        check = kwargs.get("check", True)
+        lazy = check == "lazy"
+        if lazy:
+            _poll_checks()
+            cones = tight_ctrs.ctrs if isinstance(tight_ctrs, PreparedCones) else tight_ctrs
+            if isinstance(cones, torch.Tensor) and (int(cones.shape[1]), int(cones.shape[2])) not in qpsolver._apgd_cap:
+                lazy = False
+        o = _apgd_op(tight_ctrs, pred_cost, mode, sign, kwargs, bool(check) and not lazy, ("loss", "grad"))
+        loss, grad = o["loss"], o["grad"]
+        if lazy:
+            sparse = isinstance(tight_ctrs, SparseCones) or (isinstance(tight_ctrs, PreparedCones) and tight_ctrs.sparse)
+            _defer_check(o["status"], "solver='hip' (lazy check, apgd" + (", sparse cones)" if sparse else ")"))
+            ok = o["status"] == 0
+            loss = torch.where(ok, loss, torch.zeros_like(loss))
+            grad = torch.where(ok.unsqueeze(1), grad, torch.zeros_like(grad))
+        ctx.save_for_backward(grad)
+        ctx.pred_meta = (pred_cost.device, pred_cost.dtype)
+        return loss.to(device=pred_cost.device, dtype=pred_cost.dtype)
+
+    @staticmethod
     def backward(ctx, grad_out):
         (grad,) = ctx.saved_tensors
         device, dtype = ctx.pred_meta
@@ -240,7 +288,7 @@ class abstractConeAlignedCosine(optModule):
         sign = sense_sign(self.optmodel.modelSense)  # ValueError on a bad sense, src/cave.py:62-67
         kwargs = self._solver_kwargs_for_call()
         mode = self._mode()
-        if kwargs.get("warm_start"):
+        if kwargs.get("warm_start") and not kwargs.get("_apgd"):  # (the APGD arm runs cold: no cache is made for it)
             kwargs = dict(kwargs, warm_start=self._warm_cache(tight_ctrs, mode, kwargs))
         loss = _ConeLossFunction.apply(pred_cost, tight_ctrs, mode, sign, self._inner_ratio(), kwargs)
         return self._reduce(loss)
@@ -296,16 +344,22 @@ class abstractConeAlignedCosine(optModule):
         """The constant target for an already sense-flipped cost (src/cave.py:121-129,197-219)."""
         if isinstance(tight_ctrs, PreparedCones):
             tight_ctrs = tight_ctrs.ctrs  # the batch it was prepared from (the target needs no fused step)
+        kw = self._solver_kwargs_for_call()
+        mode = self._mode()
+        if kw.get("_apgd") and mode == _lib.MODE_EXACT:
+            with torch.no_grad():
+                o = _apgd_op(tight_ctrs, signed_cost, mode, 1.0, kw, kw.get("check", True) is True, ("target",))
+            return o["target"].to(device=signed_cost.device, dtype=signed_cost.dtype)
         with torch.no_grad():
             if isinstance(tight_ctrs, PackedBatch):
-                o = tight_ctrs.store.cone_op(tight_ctrs.ids, signed_cost, self._mode(), 1.0, self._inner_ratio(),
-                                             outputs=("target",), **_packed_kwargs(self._solver_kwargs_for_call()))
+                o = tight_ctrs.store.cone_op(tight_ctrs.ids, signed_cost, mode, 1.0, self._inner_ratio(),
+                                             outputs=("target",), **_packed_kwargs(kw))
             elif isinstance(tight_ctrs, SparseCones):
-                o = cone_op_sparse(tight_ctrs, signed_cost, self._mode(), 1.0, self._inner_ratio(),
-                                   outputs=("target",), **_packed_kwargs(self._solver_kwargs_for_call()))
+                o = cone_op_sparse(tight_ctrs, signed_cost, mode, 1.0, self._inner_ratio(),
+                                   outputs=("target",), **_packed_kwargs(kw))
             else:
-                o = cone_op_dense(tight_ctrs, signed_cost, self._mode(), 1.0, self._inner_ratio(),
-                                  outputs=("target",), **_op_kwargs(self._solver_kwargs_for_call()))
+                o = cone_op_dense(tight_ctrs, signed_cost, mode, 1.0, self._inner_ratio(),
+                                  outputs=("target",), **_op_kwargs(kw))
         return o["target"].to(device=signed_cost.device, dtype=signed_cost.dtype)
 
 
@@ -344,6 +398,16 @@ class innerConeAlignedCosine(exactConeAlignedCosine):
     path-following steps on the barrier problem (CAVE_MODE_INNER_IPM, include/cave_hip.h), every multiplier of
     the iterate strictly positive, the normalised iterate is the target and no average normal is mixed in.
     A restatement of the mechanism, not of Clarabel's iterates (no Clarabel in the image: parity unpinned).
+
+    ``solver_kwargs={'inner': 'apgd'}``: the interior point is the truncated iterate of the reference's APGD projector
+    (`project_apgd`, src/qpsolver.py:11-110, what the reference's CaVE+ runs under ``solver='apgd'``), restated on the
+    device (cave_hip_cone_apgd, include/cave_hip.h) and pinned against the unmodified reference by fixtures.  The keys
+    ``max_iters`` (default 200), ``tol_grad`` (default None), ``check_frequency`` and ``power_iter`` keep the reference's
+    names; the constructor's ``max_iter`` is ignored on this arm, as in the reference.  Takes dense tensors and
+    SparseCones (a PreparedCones is unwrapped); a PackedBatch raises ValueError (its store holds reduced cones);
+    ``warm_start`` runs cold and makes no cache.  ``check=True`` (default) reads the status of the first chunk back, which
+    is every chunk's; with ``tol_grad=None`` nothing else is read on the host, and ``check=False`` / ``'lazy'`` read nothing.
+    The arm belongs to this class: exactConeAlignedCosine ignores ``'inner'``, as it always has.
     """
 
     _INNER_DEFAULTS: dict[str, dict] = {"hip": {}}
@@ -359,8 +423,8 @@ class innerConeAlignedCosine(exactConeAlignedCosine):
         if not 0 <= inner_ratio <= 1:
             raise ValueError(f"Invalid inner_ratio {inner_ratio}. It should be between 0 and 1.")
         self.inner = str(self.solver_kwargs.get("inner", "push"))
-        if self.inner not in ("push", "ipm"):
-            raise ValueError(f"Invalid solver_kwargs['inner'] {self.inner!r}. It should be 'push' or 'ipm'.")
+        if self.inner not in ("push", "ipm", "apgd"):
+            raise ValueError(f"Invalid solver_kwargs['inner'] {self.inner!r}. It should be 'push', 'ipm' or 'apgd'.")
         self.max_iter = int(max_iter)
         self.solve_ratio = float(solve_ratio)
         self.inner_ratio = float(inner_ratio)
@@ -372,11 +436,15 @@ class innerConeAlignedCosine(exactConeAlignedCosine):
         # under data parallelism every rank must construct the module with the same seed
         if self._branch_rng.uniform() > self.solve_ratio:
             return _lib.MODE_HEURISTIC
+        if self.inner == "apgd":  # the normalised APGD iterate is the target: the epilogue of MODE_EXACT (src/cave.py:213-214)
+            return _lib.MODE_EXACT
         return _lib.MODE_INNER_IPM if self.inner == "ipm" else _lib.MODE_INNER
 
     def _solver_kwargs_for_call(self) -> dict:
         if self.inner == "ipm":  # max_iter is honoured: it is the number of interior-point steps
             return dict(self.solver_kwargs, max_iter=max(1, self.max_iter))
+        if self.inner == "apgd":  # the class, not the key, chooses the arm: exactConeAlignedCosine ignores 'inner' as before
+            return dict(self.solver_kwargs, _apgd=True)
         return self.solver_kwargs
 
     def _inner_ratio(self) -> float:

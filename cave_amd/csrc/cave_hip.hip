@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include "kernels.h"
+#include "apgd.h"
 #include "cone_entry.h"
 #include "sp_grid.h"
 #include "tight_cones.h"
@@ -504,6 +505,44 @@ int32_t cave_hip_tight_cones_fill(const cave_lin_system* sys, const cave_lin_sys
                                   int64_t N, double tol, const int64_t* ent_off, int64_t ent_cap, uint32_t* key, float* val,
                                   int32_t* status, void* stream) {
   return tight_cones_entry(true, sys, lazy, lazy_off, sol, N, tol, nullptr, nullptr, ent_off, ent_cap, key, val, status, stream);
+}
+
+// ------------------------------------------------------------------ APGD projector (apgd.h)
+
+int32_t cave_hip_apgd_lds_bytes(int64_t m_max, int64_t d, int64_t nnz_cap) { return (int32_t)apgd_lds_bytes(m_max, d, nnz_cap); }
+
+static int32_t apgd_entry(bool sparse, const float* ctrs, const cave_sparse_cones* cones, const float* pred, int64_t B, int64_t m_max,
+                          int64_t d, int32_t mode, float sign, int32_t k_start, int32_t n_iter, int32_t power_iter, int32_t nnz_cap,
+                          double* x_curr, double* x_prev, double* step, float* proj, float* rnorm, float* target, float* loss,
+                          float* grad, int32_t* status, int32_t* iters, double* pgrad, void* stream) {
+  ApgdParams P;
+  int64_t grid;
+  int waves;
+  char msg[kSolverMsg];
+  const int32_t rc = apgd_plan(sparse, ctrs, cones, pred, B, m_max, d, mode, sign, k_start, n_iter, power_iter, nnz_cap, x_curr, x_prev,
+                               step, proj, rnorm, target, loss, grad, status, iters, pgrad, &P, &grid, &waves, msg);
+  if (rc != CAVE_OK) return fail(rc, msg);
+  if (grid == 0) return CAVE_OK;
+  hipError_t e = waves == 1 ? launch_apgd_w1(sparse, (unsigned)grid, (hipStream_t)stream, P)
+                            : launch_apgd_w4(sparse, (unsigned)grid, (hipStream_t)stream, P);
+  if (e != hipSuccess) return fail(CAVE_E_LAUNCH, "launch apgd kernel", e);
+  return CAVE_OK;
+}
+
+int32_t cave_hip_cone_apgd(const float* ctrs, const float* pred, int64_t B, int64_t m_max, int64_t d, int32_t mode, float sign,
+                           int32_t k_start, int32_t n_iter, int32_t power_iter, int32_t nnz_cap, double* x_curr, double* x_prev,
+                           double* step, float* proj, float* rnorm, float* target, float* loss, float* grad, int32_t* status,
+                           int32_t* iters, double* pgrad, void* stream) {
+  return apgd_entry(false, ctrs, nullptr, pred, B, m_max, d, mode, sign, k_start, n_iter, power_iter, nnz_cap, x_curr, x_prev, step, proj,
+                    rnorm, target, loss, grad, status, iters, pgrad, stream);
+}
+
+int32_t cave_hip_cone_apgd_sparse(const cave_sparse_cones* cones, const float* pred, int32_t mode, float sign, int32_t k_start,
+                                  int32_t n_iter, int32_t power_iter, int32_t nnz_cap, double* x_curr, double* x_prev, double* step,
+                                  float* proj, float* rnorm, float* target, float* loss, float* grad, int32_t* status,
+                                  int32_t* iters, double* pgrad, void* stream) {
+  return apgd_entry(true, nullptr, cones, pred, 0, 0, 0, mode, sign, k_start, n_iter, power_iter, nnz_cap, x_curr, x_prev, step, proj,
+                    rnorm, target, loss, grad, status, iters, pgrad, stream);
 }
 
 }  // extern "C"

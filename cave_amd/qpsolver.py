@@ -26,7 +26,8 @@ from ._lib import (MODE_AVG, MODE_EXACT, MODE_HEURISTIC, MODE_INNER, MODE_PROJEC
 from .sparse import SparseCones
 
 __all__ = ["project_hip", "average_ctrs_hip", "cone_op_dense", "HipSolverError", "PreparedCones", "prepare_dense",
-           "prepare_sparse", "prepare_cones", "cone_op_prepared", "step_lds_bytes", "cone_op_sparse", "project_hip_sparse"]
+           "prepare_sparse", "prepare_cones", "cone_op_prepared", "step_lds_bytes", "cone_op_sparse", "project_hip_sparse",
+           "cone_op_apgd", "cone_op_apgd_sparse", "project_apgd_hip"]
 
 
 class HipSolverError(RuntimeError):
@@ -85,6 +86,7 @@ def forget_shape(m: int, d: int) -> None:
     _split_ok.pop(key, None)
     _sparse_split_ok.pop(key, None)
     _step_ok.pop(key, None)
+    _apgd_cap.pop(key, None)
     _settled.discard(key)
 
 
@@ -646,6 +648,205 @@ def project_hip_sparse(cones, signed_cost: torch.Tensor, max_iter: int = 0, chec
     o = cone_op_sparse(cones, signed_cost, MODE_PROJECT, 1.0, 0.0, max_iter=max_iter, check=check, outputs=("proj", "rnorm"))
     device, dtype = signed_cost.device, signed_cost.dtype
     return o["proj"].to(device=device, dtype=dtype), o["rnorm"].to(device=device, dtype=dtype)
+
+
+# ---- the APGD projector (cave_hip_cone_apgd / cave_hip_cone_apgd_sparse, cave_amd/csrc/apgd.h): the reference's
+# `project_apgd` (src/qpsolver.py:11-110) restated on the device.  It iterates on the rows of the wire format as they are
+# (pairs, unit rows, repeated rows, padding), so it reads the two wire formats themselves and never a store.
+APGD_MAX_ITERS = 10_000  # the reference's cap when max_iters is None (src/qpsolver.py:23)
+_apgd_cap: dict[tuple[int, int], int] = {}  # (m_max, d) -> the entry capacity a checked dense call settled
+
+
+_apgd_full: dict[tuple[int, int], int] = {}
+
+
+def apgd_full_cap(m: int, d: int) -> int:
+    """The largest entry capacity whose arena fits the 160 KiB of LDS at this shape (0: none does); found once per shape."""
+    key = (int(m), int(d))
+    if key not in _apgd_full:
+        _apgd_full[key] = _apgd_full_cap_search(*key)
+    return _apgd_full[key]
+
+
+def _apgd_full_cap_search(m: int, d: int) -> int:
+    lib = _lib.load_library()
+    hi = min(m * d, _lib.MAX_LDS // 14)
+    if hi < 1 or lib.cave_hip_apgd_lds_bytes(m, d, 1) < 0:
+        return 0
+    lo = 1  # (fits)
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        if lib.cave_hip_apgd_lds_bytes(m, d, mid) > 0:
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo
+
+
+def _apgd_limit_error(m: int, d: int, cap: int) -> "HipSolverError":
+    return HipSolverError(f"solver='hip' (apgd): an instance with more than {cap} non-zeros does not fit the 160 KiB LDS arena "
+                          f"of the APGD kernel at m_max = {m}, d = {d} (28 m_max + 20 d + 14 nnz bytes).")
+
+
+def _apgd_launch(cones, pred, B, m, d, mode, sign, k_start, n_iter, power_iter, cap, state, want_pgrad, outputs, dev):
+    lib = _lib.load()
+    out, status, iters = _alloc_out(outputs, B, d, dev)
+    if state is None and k_start == 0:
+        state = (torch.empty(B, m, dtype=torch.float64, device=dev), torch.empty(B, m, dtype=torch.float64, device=dev),
+                 torch.empty(B, dtype=torch.float64, device=dev))
+    out["state"] = state
+    pgrad = out["pgrad"] = torch.empty(B, dtype=torch.float64, device=dev) if want_pgrad else None
+    ptr = _lib.ptr
+    tail = (int(mode), float(sign), int(k_start), int(n_iter), int(power_iter), int(cap), *(ptr(t) for t in (state or (None,) * 3)),
+            *_out_ptrs(out, status, iters), ptr(pgrad), _lib.current_stream())
+    if isinstance(cones, SparseCones):
+        rc, what = lib.cave_hip_cone_apgd_sparse(cones.c_ref(), ptr(pred), *tail), "cave_hip_cone_apgd_sparse"
+    else:
+        rc, what = lib.cave_hip_cone_apgd(ptr(cones), ptr(pred), B, m, d, *tail), "cave_hip_cone_apgd"
+    _lib.check(rc, what)
+    return out
+
+
+def _apgd_empty(outputs, m: int, d: int, dev, want_pgrad: bool) -> dict:
+    """What a launch returns for an empty batch (the C ABI answers B == 0 with CAVE_OK and touches nothing)."""
+    out = _alloc_out(outputs, 0, d, dev)[0]
+    out["state"] = (torch.empty(0, m, dtype=torch.float64, device=dev), torch.empty(0, m, dtype=torch.float64, device=dev),
+                    torch.empty(0, dtype=torch.float64, device=dev))
+    out["pgrad"] = torch.empty(0, dtype=torch.float64, device=dev) if want_pgrad else None
+    return out
+
+
+def _apgd_state_ok(state, B: int, m: int, dev) -> None:
+    if state is None:
+        return
+    xc, xp, st = state
+    for t, shape in ((xc, (B, m)), (xp, (B, m)), (st, (B,))):
+        if t.dtype != torch.float64 or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"state: need contiguous float64 tensors x_curr ({B}, {m}), x_prev ({B}, {m}), step ({B},) on {dev}")
+
+
+def cone_op_apgd(tight_ctrs: torch.Tensor, pred_cost: torch.Tensor, mode: int = MODE_PROJECT, sign: float = 1.0, *,
+                 n_iter: int = 200, k_start: int = 0, power_iter: int = 8, nnz_cap: int = 0, state=None, pgrad: bool = False,
+                 check: bool = True, outputs: tuple[str, ...] = ("proj", "rnorm")) -> dict:
+    """`n_iter` APGD iterations per instance on the dense wire format (cave_hip_cone_apgd), numbered from `k_start`.
+
+    -> the outputs asked for (proj / rnorm un-squared / target / loss / grad; mode MODE_PROJECT or MODE_EXACT) plus
+    "status", "iters", "state" = (x_curr [B, m_max], x_prev, step [B]) in float64 and, with ``pgrad=True``, "pgrad" [B],
+    the reference's convergence quantity.  ``k_start > 0`` continues from ``state`` (the tensors of the launch before,
+    updated in place).  ``nnz_cap`` = 0: the capacity settled for this (m_max, d) -- a guess at first; under
+    ``check=True`` a batch with an instance beyond it is retried once with the largest capacity the LDS holds, and what
+    worked is remembered.  ``check=True`` reads the status back (one host sync) and raises like cone_op_dense;
+    ``check=False`` leaves CAVE_ST_TOO_LARGE / CAVE_ST_BAD_INPUT in "status" and NaN in that instance's outputs."""
+    _lib.load()
+    if not isinstance(tight_ctrs, torch.Tensor) or tight_ctrs.dim() != 3:
+        raise ValueError("tight_ctrs must have shape (B, m_max, d)")
+    B, m, d = tight_ctrs.shape
+    dev, pred = _device_and_pred(tight_ctrs, pred_cost, B, d, mode)
+    ctrs = _as_device(tight_ctrs, dev)
+    with torch.cuda.device(dev):
+        if B == 0:
+            return _apgd_empty(outputs, m, d, dev, pgrad)
+        _apgd_state_ok(state, B, m, dev)
+        full = apgd_full_cap(m, d)
+        if full < 1:
+            raise _apgd_limit_error(m, d, 0)
+        auto = nnz_cap <= 0
+        cap = min(full, _apgd_cap.get((m, d), min(m * d, 3 * (m + d) + 64))) if auto else int(nnz_cap)
+        args = (ctrs, pred, B, m, d, mode, sign, k_start, n_iter, power_iter)
+        out = _apgd_launch(*args, cap, state, pgrad, outputs, dev)
+        if check:
+            if auto and cap < full and k_start == 0 and bool((out["status"] == ST_TOO_LARGE).any()):
+                cap = full
+                out = _apgd_launch(*args, cap, state, pgrad, outputs, dev)
+            if bool((out["status"] == ST_TOO_LARGE).any()):
+                raise _apgd_limit_error(m, d, cap)
+            _raise_for_status(out["status"], "solver='hip' (apgd)")
+            if auto:
+                _apgd_cap[(m, d)] = cap
+    return out
+
+
+def cone_op_apgd_sparse(cones, pred_cost: torch.Tensor, mode: int = MODE_PROJECT, sign: float = 1.0, *, n_iter: int = 200,
+                        k_start: int = 0, power_iter: int = 8, nnz_cap: int = 0, state=None, pgrad: bool = False,
+                        check: bool = True, outputs: tuple[str, ...] = ("proj", "rnorm")) -> dict:
+    """cone_op_apgd for a batch on the sparse wire format (cave_hip_cone_apgd_sparse): the same bits as the dense call on
+    the densified batch.  ``nnz_cap`` = 0: the entries of the largest instance (read from the offsets once per batch
+    object), at most what the LDS holds.  A malformed instance is rejected on the device (CAVE_ST_BAD_INPUT)."""
+    _lib.load()
+    if not isinstance(cones, SparseCones):
+        raise TypeError("cone_op_apgd_sparse: cones must be a SparseCones")
+    B, m, d = _shape(cones)
+    dev, pred = _device_and_pred(cones, pred_cost, B, d, mode)
+    x = cones.to(dev)
+    with torch.cuda.device(dev):
+        if B == 0:
+            return _apgd_empty(outputs, m, d, dev, pgrad)
+        _apgd_state_ok(state, B, m, dev)
+        full = apgd_full_cap(m, d) if m > 0 else 0
+        if full < 1:
+            raise _apgd_limit_error(m, d, 0)
+        if nnz_cap <= 0:
+            big = getattr(cones, "_max_nnz", None)
+            if big is None:
+                big = cones._max_nnz = int(cones.nnz_per_instance.max()) if B else 0
+            nnz_cap = min(full, max(big, 1))
+        out = _apgd_launch(x, pred, B, m, d, mode, sign, k_start, n_iter, power_iter, int(nnz_cap), state, pgrad, outputs, dev)
+        if check:
+            if bool((out["status"] == ST_TOO_LARGE).any()):
+                raise _apgd_limit_error(m, d, int(nnz_cap))
+            _raise_for_status(out["status"], "solver='hip' (apgd, sparse cones)", sparse=True)
+    return out
+
+
+def _apgd_chunks(cones, pred, mode, sign, max_iters, tol_grad, check_frequency, power_iter, check, outputs):
+    """The reference's outer loop (src/qpsolver.py:39-58): chunks of `check_frequency` iterations through the
+    continuation state; with `tol_grad` the check quantity is read on the host once per chunk and the loop stops at the
+    first chunk whose batch maximum is <= tol_grad.  -> (outputs of the last launch, chunks run, the maxima read).
+    `check` applies to the first chunk, whose status is every chunk's (the cones and the prediction do not change); an
+    empty batch runs no chunk."""
+    op = cone_op_apgd_sparse if isinstance(cones, SparseCones) else cone_op_apgd
+    if _shape(cones)[0] == 0:
+        return op(cones, pred, mode, sign, n_iter=0, pgrad=tol_grad is not None, check=check, outputs=outputs), 0, []
+    cap = APGD_MAX_ITERS if max_iters is None else int(max_iters)
+    K = int(check_frequency)
+    if K < 1:
+        raise ValueError("check_frequency must be positive")
+    out, state, seen, chunks = None, None, [], 0
+    starts = list(range(0, cap, K)) or [0]
+    for k_start in starts:
+        n = max(0, min(K, cap - k_start))
+        last = k_start == starts[-1]
+        # only the last launch needs the outputs; with tol_grad any launch may be the last
+        o = op(cones, pred, mode, sign, n_iter=n, k_start=k_start, power_iter=power_iter, state=state, pgrad=tol_grad is not None,
+               check=check if k_start == 0 else False, outputs=outputs if (last or tol_grad is not None) else ())
+        out, state, chunks = o, o["state"], chunks + 1
+        if tol_grad is not None:
+            pg = o["pgrad"]
+            worst = float(pg[~torch.isnan(pg)].max()) if bool((~torch.isnan(pg)).any()) else 0.0
+            seen.append(worst)
+            if worst <= tol_grad:
+                break
+    return out, chunks, seen
+
+
+def project_apgd_hip(tight_ctrs, signed_cost: torch.Tensor, tol_grad: float | None = 1e-4, max_iters: int | None = None,
+                     check_frequency: int = 200, power_iter: int = 8, *, check: bool = True,
+                     info: dict | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """The reference's `project_apgd` (src/qpsolver.py:11-63), signature and return values: (proj (B, d), rnorm (B,)) with
+    rnorm the SQUARED residual, on signed_cost's device and dtype.  `tight_ctrs`: a dense tensor or a SparseCones.  The
+    stopping rule is the reference's, batch-global.  With ``tol_grad=None`` there is one launch per chunk and no host read
+    between the chunks; ``check=True`` (the default, beyond the reference's signature) still reads the status of the FIRST
+    chunk back -- on the dense route that is also where the entry capacity of a new shape settles, possibly with one
+    relaunch -- and raises for an instance that failed.  ``check=False`` makes no host read at all: a failed instance
+    then holds NaN, and a dense shape runs with the capacity it has settled or the first guess.  `info` (a dict) receives
+    "chunks", the chunks run, and "pgrad", the check quantity read after each."""
+    out, chunks, seen = _apgd_chunks(tight_ctrs, signed_cost, MODE_PROJECT, 1.0, max_iters, tol_grad, check_frequency, power_iter,
+                                     check, ("proj", "rnorm"))
+    if info is not None:
+        info["chunks"], info["pgrad"] = chunks, seen
+    device, dtype = signed_cost.device, signed_cost.dtype
+    rn = out["rnorm"].to(torch.float64)
+    return out["proj"].to(device=device, dtype=dtype), (rn * rn).to(device=device, dtype=dtype)
 
 
 def average_ctrs_hip(tight_ctrs: torch.Tensor) -> torch.Tensor:

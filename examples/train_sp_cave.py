@@ -8,6 +8,7 @@ reference's CVRP model (2-degree rows, rounded-capacity cuts), solved by the dyn
     python examples/train_sp_cave.py [--grid 5 5] [--num-data 100] [--batch 32] [--epochs 10] [--packed]
     python examples/train_sp_cave.py --problem tsp --nodes 10 --packed --warm-start
     python examples/train_sp_cave.py --grid 30 30 --num-data 64 --batch 32 --epochs 3 --packed --inner ipm
+    python examples/train_sp_cave.py --inner apgd [--sparse] [--apgd-iters 200]  # CaVE+ with the reference's APGD projector on the device
     python examples/train_sp_cave.py --packed --graph          # the whole step (predictor, loss, backward, Adam) as one HIP graph
     python examples/train_sp_cave.py --problem tsp --prefetch  # dense cones: the next batch's pack rides in this batch's loss call
     python examples/train_sp_cave.py --sparse [--packed]       # cones on the sparse wire format: no dense padding anywhere
@@ -49,9 +50,12 @@ def main(argv=None):
                                                               "solver reaches the data set's optima or the regret's)")
     ap.add_argument("--capacity", type=float, default=30.0, help="CVRP: vehicle capacity (demands are uniform on [0, 10))")
     ap.add_argument("--vehicles", type=int, default=3, help="CVRP: number of vehicles")
-    ap.add_argument("--inner", default="push", choices=["push", "ipm"],
-                    help="CaVE+ interior point: 'push' (nnls-style: exact projection pushed towards the average normal) or "
-                         "'ipm' (truncated interior-point iterate, as the reference's Clarabel max_iter=3: src/cave.py:213-214)")
+    ap.add_argument("--inner", default="push", choices=["push", "ipm", "apgd"],
+                    help="CaVE+ interior point: 'push' (nnls-style: exact projection pushed towards the average normal), "
+                         "'ipm' (truncated interior-point iterate, as the reference's Clarabel max_iter=3: src/cave.py:213-214) or "
+                         "'apgd' (the truncated iterate of the reference's APGD projector, src/qpsolver.py:11-110, --apgd-iters "
+                         "iterations; dense or --sparse cones, not --packed: a store holds reduced cones)")
+    ap.add_argument("--apgd-iters", type=int, default=200, help="iterations of --inner apgd (solver_kwargs['max_iters'])")
     ap.add_argument("--max-iter", type=int, default=3, help="interior-point steps of --inner ipm")
     ap.add_argument("--warm-start", action="store_true",
                     help="start each projection from the multipliers of the previous epoch (packed store, or dense / --sparse "
@@ -94,6 +98,9 @@ def main(argv=None):
         ap.error("--problem vrp takes --nodes up to 20, and above 14 nodes it needs --device-regret and --device-data: the host's "
                  "dynamic program stops at 14 nodes, the data set's optima and the regret's exact routes then come from the device "
                  "(VRPConeDataset(..., device=), vrp_regret(..., device=))")
+    if args.inner == "apgd" and (args.packed or args.variant == "exact"):
+        ap.error("--inner apgd is for the inner and hybrid variants on dense or --sparse cones: it iterates on the rows of the "
+                 "wire format as they are, and a packed store holds reduced cones")
     sp_device = args.device_data and args.problem == "sp"
     if args.graph and (not args.packed or args.variant == "hybrid"):
         ap.error("--graph needs --packed and a variant without a per-call branch draw")
@@ -128,6 +135,8 @@ def main(argv=None):
     kw = {}
     if args.inner != "push":
         kw["inner"] = args.inner
+    if args.inner == "apgd":
+        kw["max_iters"] = args.apgd_iters
     if args.graph:
         kw["check"] = False   # (a captured step cannot read the status back; it is examined after each replay below)
     elif args.lazy_check:

@@ -626,6 +626,51 @@ int32_t cave_hip_tight_cones_fill(const cave_lin_system* sys, const cave_lin_sys
                                   const float* sol, int64_t N, double tol, const int64_t* ent_off, int64_t ent_cap,
                                   uint32_t* key, float* val, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------ APGD projector (additive to v10)
+ * The reference's accelerated projected-gradient projector (`project_apgd`, src/qpsolver.py:11-110) restated on the
+ * device, on the wire formats themselves: it iterates in the multiplier space of the ORIGINAL rows, so +a/-a pairs, unit
+ * rows, repeated rows and zero padding stay as they are (the stores hold the reduced cone and cannot serve).  Per
+ * instance, with A the m_max x d block as given and y = sign * pred, all arithmetic in fp64:
+ *   step size   v = 1/sqrt(m_max) in every row; power_iter times  u = A^T v, v = A u, v /= max(||v||, 1e-8);
+ *               s = 1 / max(||A^T v||^2, 1e-8)                                        (m_max is the batch's)
+ *   iterations  from x_curr = x_prev = 0, for k = k_start .. k_start + n_iter - 1 with beta_k = (k-2)/(k+1), beta_0 = 0:
+ *               y_k = x_curr + beta_k (x_curr - x_prev);  g = A (A^T y_k - y);  x_prev = x_curr;  x_curr = max(y_k - s g, 0)
+ * Arguments:
+ *   ctrs, pred, B, m_max, d   as cave_hip_cone_dense (1 <= m_max, d <= 65535), or `cones` on the sparse wire format
+ *   mode        CAVE_MODE_PROJECT (writes proj, rnorm) or CAVE_MODE_EXACT (also target = proj / max(||proj||, 1e-8),
+ *               loss = 1 - cos(y, target) and grad, the epilogue that mode has everywhere; src/cave.py:129,213-214)
+ *   sign        +1 or -1
+ *   k_start     0: the launch computes the step size and starts from zero; > 0: it continues from the state
+ *   n_iter      iterations of this launch, 0 .. 100000;   power_iter  0 .. 64
+ *   nnz_cap     entries per instance the LDS arena holds, 1 .. m_max * d, with cave_hip_apgd_lds_bytes(m_max, d, nnz_cap) > 0
+ *   x_curr, x_prev [B, m_max] fp64, step [B] fp64   caller-owned state, all three or none: read when k_start > 0 (then
+ *               required), written back by every launch that is given them
+ *   proj, rnorm (un-squared), target, loss, grad, status, iters   as cave_hip_cone_dense, any may be NULL; iters = n_iter
+ *   pgrad [B] fp64 or NULL   the reference's check quantity (src/qpsolver.py:52-57):
+ *               max_i (x_i > 0 ? |g_i| : max(-g_i, 0)) with g = A (A^T x_curr - y)
+ * Per-instance status: CAVE_ST_BAD_INPUT for a non-finite prediction or dense entry, or a sparse entry that breaks the
+ * contract of cave_sparse_cones; CAVE_ST_TOO_LARGE for more than nnz_cap entries.  A failed instance gets NaN in every
+ * float output and in pgrad, iters 0, and its state is left alone; the other instances are unaffected.
+ * One workgroup per instance, of one wave, or of four when m_max, d or nnz_cap exceeds 512.  Every row sum and column sum
+ * is accumulated by one lane in index order, without atomics: results are bit-reproducible, do not depend on the batch,
+ * on the position in it, on the wire format or on the workgroup size, and a chain of launches through the state equals
+ * the single launch bit for bit.  No loop bound depends on the values.  B == 0: nothing to do, CAVE_OK.
+ * CAVE_E_INVALID before any launch: a shape, mode, sign, k_start (> 2^30), n_iter, power_iter or nnz_cap out of range; an
+ * arena beyond 160 KiB; a null or misaligned pred / ctrs / ent_off / key / val; a partial state, a continuation without
+ * state, a misaligned state or pgrad; B >= 2^31.
+ * cave_hip_apgd_lds_bytes: the LDS arena of one workgroup, 28 m_max + 20 d + 14 nnz_cap bytes and change (TSP-20, m_max
+ * 235, d 190, 1617 entries: 33168, four workgroups per compute unit; SP 5x5, 90 x 40, 256 entries: 6992), or -1
+ * where a shape or capacity is out of range or the arena exceeds 160 KiB (at TSP-20's shape: beyond about 10 900 entries). */
+int32_t cave_hip_apgd_lds_bytes(int64_t m_max, int64_t d, int64_t nnz_cap);
+int32_t cave_hip_cone_apgd(const float* ctrs, const float* pred, int64_t B, int64_t m_max, int64_t d, int32_t mode, float sign,
+                           int32_t k_start, int32_t n_iter, int32_t power_iter, int32_t nnz_cap, double* x_curr, double* x_prev,
+                           double* step, float* proj, float* rnorm, float* target, float* loss, float* grad, int32_t* status,
+                           int32_t* iters, double* pgrad, void* stream);
+int32_t cave_hip_cone_apgd_sparse(const cave_sparse_cones* cones, const float* pred, int32_t mode, float sign, int32_t k_start,
+                                  int32_t n_iter, int32_t power_iter, int32_t nnz_cap, double* x_curr, double* x_prev, double* step,
+                                  float* proj, float* rnorm, float* target, float* loss, float* grad, int32_t* status,
+                                  int32_t* iters, double* pgrad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
