@@ -13,18 +13,15 @@ import ctypes as C
 import os
 import subprocess
 
+from . import _build
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.path.join(_HERE, "libcave_hip.so")
 _CSRC = os.path.join(_HERE, "csrc")
-_HEADERS = [os.path.join(_CSRC, n) for n in ("kernels.h", "cone_common.h", "cone_core.h", "cone_band.h", "cone_dense.h", "cone_rb.h", "cone_instance.h", "cone_step.h", "cone_entry.h",
-                                             "wave_prims.h", "ctx_wave.h", "ctx_block.h", "solver_entry.h", "sp_grid.h", "tight_cones.h", "tsp_hk.h", "vrp_dp.h", "tsp_hk_wide.h", "vrp_dp_wide.h", "apgd.h")] + \
-    [os.path.join(_ROOT, "include", "cave_hip.h")]
 # translation units: the C ABI (host code) + one file per kernel shape (cave_amd/csrc/kernels.h)
 _UNITS = ["cave_hip"] + [f"k_{op}_w{w}" for op in ("dense", "pack", "packed") for w in (1, 2, 4, 8)] + \
     ["k_large_dense", "k_large_pack", "k_large_packed_w1", "k_large_packed_w2", "k_large_packed_w4", "k_step",
      "k_step_warm", "k_step_sparse", "k_step_sparse_warm", "k_step_ipm", "k_step_sparse_ipm", "k_pack_sparse_w2", "k_pack_sparse_w4", "k_pack_sparse_w8", "k_large_pack_sparse", "k_sp_grid", "k_tight_cones", "k_tsp_hk", "k_vrp_dp", "k_tsp_hk_wide", "k_vrp_dp_wide", "k_apgd_w1", "k_apgd_w4"]
-_SOURCES = [os.path.join(_CSRC, u + ".hip") for u in _UNITS] + _HEADERS
 _OBJ_DIR = os.path.join(_CSRC, "build")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 
@@ -56,27 +53,20 @@ def build(force: bool = False, verbose: bool = False, jobs: int | None = None) -
     """hipcc --offload-arch=gfx950 -> cave_amd/libcave_hip.so (in-tree; cross-compiles without a GPU).
 
     Every kernel shape is its own translation unit (objects under cave_amd/csrc/build/): they compile in
-    parallel and only the units older than their sources are rebuilt."""
+    parallel and only the units older than a file they read (_build.stale) are rebuilt."""
     from concurrent.futures import ThreadPoolExecutor
 
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(_OBJ_DIR, exist_ok=True)
-    newest_hdr = max(os.path.getmtime(p) for p in _HEADERS)
-    todo, objs = [], []
-    for u in _UNITS:
-        src, obj = os.path.join(_CSRC, u + ".hip"), os.path.join(_OBJ_DIR, u + ".o")
-        objs.append(obj)
-        if force or not os.path.exists(obj) or os.path.getmtime(obj) < max(newest_hdr, os.path.getmtime(src)):
-            todo.append((src, obj))
-    if not todo and os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(o) for o in objs):
+    units = [(os.path.join(_CSRC, u + ".hip"), os.path.join(_OBJ_DIR, u + ".o")) for u in _UNITS]
+    objs = [obj for _, obj in units]
+    todo = [job for job in units if force or _build.stale(job[1])]
+    if not todo and not _build.older(LIB_PATH, objs):
         return LIB_PATH
 
     def compile_one(job):
         src, obj = job
-        cmd = [hipcc, *HIPCC_FLAGS, "-c", src, "-o", obj]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.run(cmd, check=True)
+        _build.run([hipcc, *HIPCC_FLAGS, "-c", src, "-o", obj], src, obj, verbose)
 
     if jobs is None:
         jobs = max(1, min(len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 4, 8))

@@ -27,9 +27,10 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+from cave_amd import _build
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -39,9 +40,7 @@ def build(force: bool = False) -> str:
     """Compile oracle/nnls_oracle.c -> oracle/liboracle.so with gcc (seconds)."""
     so = os.path.join(_HERE, "liboracle.so")
     src = os.path.join(_HERE, "nnls_oracle.c")
-    if force or not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-        subprocess.run(["gcc", "-O2", "-fPIC", "-std=c11", "-shared", src, "-o", so, "-lm"], check=True)
-    return so
+    return _build.make(["gcc", "-O2", "-fPIC", "-std=c11", "-shared", src, "-o", so, "-lm"], src, so, force)
 
 
 def _lib():

@@ -18,7 +18,6 @@ from cave_amd._lib import SparseConesC
 from emul_solver_common import _p
 
 _SRC = "simt_apgd.cpp"
-_DEPS = common.deps(_SRC, "apgd.h", "wave_prims.h")
 
 # (name, dtype, flag bit, shape of (B, m, d))
 TABLE = (("proj", np.float32, 1, lambda B, m, d: (B, d)), ("rnorm", np.float32, 1, lambda B, m, d: (B,)),
@@ -31,7 +30,7 @@ FLOAT_OUT = ("proj", "rnorm", "target", "loss", "grad")
 
 
 def build(asan: bool = False) -> str:
-    return common.build(_SRC, _DEPS, "APGD_MAIN", asan)
+    return common.build(_SRC, "APGD_MAIN", asan)
 
 
 class SimtApgd:

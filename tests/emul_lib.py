@@ -10,49 +10,47 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+from cave_amd import _build
+from cave_amd._lib import LiteStore, Store, WarmCacheC  # the structs of include/cave_hip.h, here over host arrays
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, "emul", "emul_abi.cpp")
-_DEPS = [
-    _SRC,
-    os.path.join(_HERE, "..", "cave_amd", "csrc", "cone_band.h"),
-    os.path.join(_HERE, "..", "cave_amd", "csrc", "cone_dense.h"),
-    os.path.join(_HERE, "..", "cave_amd", "csrc", "cone_rb.h"),
-    os.path.join(_HERE, "emul", "ctx_serial.h"),
-    os.path.join(_HERE, "..", "cave_amd", "csrc", "cone_core.h"),
-    os.path.join(_HERE, "..", "cave_amd", "csrc", "cone_common.h"),
-    os.path.join(_HERE, "..", "cave_amd", "csrc", "cone_instance.h"),
-    os.path.join(_HERE, "..", "cave_amd", "csrc", "cone_step.h"),
-    os.path.join(_HERE, "..", "cave_amd", "csrc", "cone_entry.h"),
-    os.path.join(_HERE, "..", "include", "cave_hip.h"),
-]
 
 
 def build(asan: bool = False) -> str:
     out = os.path.join(_HERE, "emul", "_emul_asan.so" if asan else "_emul.so")
-    newest = max(os.path.getmtime(p) for p in _DEPS)
-    if os.path.exists(out) and os.path.getmtime(out) >= newest:
-        return out
     flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer"] if asan else ["-O2"]
-    cmd = ["g++", "-std=c++17", "-fPIC", "-shared", "-w", *flags, _SRC, "-o", out]
-    subprocess.run(cmd, check=True)
-    return out
+    return _build.make(["g++", "-std=c++17", "-fPIC", "-shared", "-w", *flags, _SRC, "-o", out], _SRC, out)
 
 
-class Store(C.Structure):
-    _fields_ = [
-        ("n", C.c_int64), ("d", C.c_int32), ("reserved", C.c_int32),
-        ("row_off", C.c_void_p), ("nnz_off", C.c_void_p), ("n_valid", C.c_void_p), ("flags", C.c_void_p),
-        ("usign", C.c_void_p), ("avg", C.c_void_p), ("vkind", C.c_void_p),
-        ("rlo", C.c_void_p), ("rhi", C.c_void_p), ("ccol", C.c_void_p), ("cval", C.c_void_p),
-        ("cptr", C.c_void_p), ("cvar", C.c_void_p), ("cvalc", C.c_void_p),
-        ("n_rows", C.c_void_p), ("n_nnz", C.c_void_p),  # slot mode only (NULL in an exact-fit store)
-        ("warm_theta", C.c_void_p), ("warm_state", C.c_void_p),  # warm start (NULL: off)
-        ("rb_cache", C.c_void_p), ("rb_stride", C.c_int64),  # red-black cache of the large path (NULL: off)
-    ]
+def outs(B, d):
+    """the seven outputs of a cone entry point, zeroed"""
+    return {
+        "proj": np.zeros((B, d), np.float32), "rnorm": np.zeros(B, np.float32),
+        "target": np.zeros((B, d), np.float32), "loss": np.zeros(B, np.float32),
+        "grad": np.zeros((B, d), np.float32), "status": np.zeros(B, np.int32),
+        "iters": np.zeros(B, np.int32),
+    }
+
+
+def host_store(n_rows, n_nnz, d):
+    """Exact-fit host store for the given per-instance counts: (Store, arrays)."""
+    B = len(n_rows)
+    row_off = np.concatenate([[0], np.cumsum(n_rows, dtype=np.int64)]).astype(np.int64)
+    nnz_off = np.concatenate([[0], np.cumsum(n_nnz, dtype=np.int64)]).astype(np.int64)
+    R, Z = int(row_off[-1]), int(nnz_off[-1])
+    arrs = {
+        "row_off": row_off, "nnz_off": nnz_off, "n_valid": np.zeros(B, np.int32), "flags": np.zeros(B, np.uint8),
+        "usign": np.zeros(B * d, np.uint8), "avg": np.zeros(B * d, np.float32),
+        "vkind": np.zeros(max(R, 1), np.uint8), "rlo": np.zeros(max(R, 1), np.uint32),
+        "rhi": np.zeros(max(R, 1), np.uint32), "ccol": np.zeros(max(Z, 1), np.uint16),
+        "cval": np.zeros(max(Z, 1), np.float32), "cptr": np.zeros(B * (d + 1), np.uint32),
+        "cvar": np.zeros(max(Z, 1), np.uint16), "cvalc": np.zeros(max(Z, 1), np.float32),
+    }
+    return Store(n=B, d=d, reserved=0, **{k: v.ctypes.data for k, v in arrs.items()}), arrs
 
 
 def _p(a):
@@ -73,12 +71,7 @@ class Emul:
         ctrs = np.ascontiguousarray(ctrs, dtype=np.float32)
         B, m, d = ctrs.shape
         pred = None if pred is None else np.ascontiguousarray(pred, dtype=np.float32)
-        out = {
-            "proj": np.zeros((B, d), np.float32), "rnorm": np.zeros(B, np.float32),
-            "target": np.zeros((B, d), np.float32), "loss": np.zeros(B, np.float32),
-            "grad": np.zeros((B, d), np.float32), "status": np.zeros(B, np.int32),
-            "iters": np.zeros(B, np.int32),
-        }
+        out = outs(B, d)
         rc = self.lib.cave_emul_cone_dense(
             _p(ctrs), _p(pred), C.c_int64(B), C.c_int64(m), C.c_int64(d), C.c_int32(mode),
             C.c_float(sign), C.c_float(inner_ratio), C.c_int32(max_iter), C.c_int32(nnz_cap), C.c_int32(lds_bytes),
@@ -94,18 +87,7 @@ class Emul:
         rc = self.lib.cave_emul_pack_count(_p(ctrs), C.c_int64(B), C.c_int64(m), C.c_int64(d), C.c_int32(nnz_cap),
                                            C.c_int32(lds_bytes), _p(n_rows), _p(n_nnz), _p(status))
         assert rc == 0 and (status == 0).all(), (rc, status)
-        row_off = np.concatenate([[0], np.cumsum(n_rows, dtype=np.int64)]).astype(np.int64)
-        nnz_off = np.concatenate([[0], np.cumsum(n_nnz, dtype=np.int64)]).astype(np.int64)
-        R, Z = int(row_off[-1]), int(nnz_off[-1])
-        arrs = {
-            "row_off": row_off, "nnz_off": nnz_off, "n_valid": np.zeros(B, np.int32), "flags": np.zeros(B, np.uint8),
-            "usign": np.zeros(B * d, np.uint8), "avg": np.zeros(B * d, np.float32),
-            "vkind": np.zeros(max(R, 1), np.uint8), "rlo": np.zeros(max(R, 1), np.uint32),
-            "rhi": np.zeros(max(R, 1), np.uint32), "ccol": np.zeros(max(Z, 1), np.uint16),
-            "cval": np.zeros(max(Z, 1), np.float32), "cptr": np.zeros(B * (d + 1), np.uint32),
-            "cvar": np.zeros(max(Z, 1), np.uint16), "cvalc": np.zeros(max(Z, 1), np.float32),
-        }
-        st = Store(n=B, d=d, reserved=0, **{k: v.ctypes.data for k, v in arrs.items()})
+        st, arrs = host_store(n_rows, n_nnz, d)
         rc = self.lib.cave_emul_pack_fill(_p(ctrs), C.c_int64(B), C.c_int64(m), C.c_int64(d), C.c_int32(nnz_cap),
                                           C.c_int32(lds_bytes), C.byref(st), C.c_int64(0), _p(status))
         assert rc == 0 and (status == 0).all(), (rc, status)
@@ -119,12 +101,7 @@ class Emul:
         all_pm1 = int(bool((arrs["flags"] & 1).all()))
         lds = self.lib.cave_emul_packed_lds_bytes(C.c_int64(d), C.c_int32(max_rows), C.c_int32(max_nnz), C.c_int32(all_pm1))
         assert lds > 0
-        out = {
-            "proj": np.zeros((B, d), np.float32), "rnorm": np.zeros(B, np.float32),
-            "target": np.zeros((B, d), np.float32), "loss": np.zeros(B, np.float32),
-            "grad": np.zeros((B, d), np.float32), "status": np.zeros(B, np.int32),
-            "iters": np.zeros(B, np.int32),
-        }
+        out = outs(B, d)
         rc = self.lib.cave_emul_cone_packed(
             C.byref(store), _p(ids), _p(pred), C.c_int64(B), C.c_int32(mode), C.c_float(sign),
             C.c_float(inner_ratio), C.c_int32(max_iter), C.c_int32(lds),
@@ -134,14 +111,6 @@ class Emul:
         return out
 
     # ---- large-cone path (global-workspace arena, band Newton systems)
-    def _outs(self, B, d):
-        return {
-            "proj": np.zeros((B, d), np.float32), "rnorm": np.zeros(B, np.float32),
-            "target": np.zeros((B, d), np.float32), "loss": np.zeros(B, np.float32),
-            "grad": np.zeros((B, d), np.float32), "status": np.zeros(B, np.int32),
-            "iters": np.zeros(B, np.int32),
-        }
-
     def large_slice_bytes(self, m, d, nnz_cap, band):
         self.lib.cave_emul_large_slice_bytes.restype = C.c_int64
         return int(self.lib.cave_emul_large_slice_bytes(C.c_int64(m), C.c_int64(d), C.c_int64(nnz_cap), C.c_int64(band)))
@@ -154,7 +123,7 @@ class Emul:
         nnz_cap = nnz_cap or max(64, int((ctrs != 0).reshape(B, -1).sum(1).max(initial=0)))
         band = band or 32 * d + 4096
         slice_bytes = slice_bytes or self.large_slice_bytes(m, d, nnz_cap, band)
-        out = self._outs(B, d)
+        out = outs(B, d)
         rc = self.lib.cave_emul_cone_dense_large(
             _p(ctrs), _p(pred), C.c_int64(B), C.c_int64(m), C.c_int64(d), C.c_int32(mode), C.c_float(sign),
             C.c_float(inner_ratio), C.c_int32(max_iter), C.c_int64(nnz_cap), C.c_int32(lds_bytes), C.c_int64(slice_bytes),
@@ -172,18 +141,7 @@ class Emul:
         rc = self.lib.cave_emul_pack_large(_p(ctrs), C.c_int64(B), C.c_int64(m), C.c_int64(d), C.c_int64(nnz_cap),
                                            C.c_int64(slice_bytes), _p(n_rows), _p(n_nnz), None, C.c_int64(0), _p(status))
         assert rc == 0 and (status == 0).all(), (rc, status)
-        row_off = np.concatenate([[0], np.cumsum(n_rows, dtype=np.int64)]).astype(np.int64)
-        nnz_off = np.concatenate([[0], np.cumsum(n_nnz, dtype=np.int64)]).astype(np.int64)
-        R, Z = int(row_off[-1]), int(nnz_off[-1])
-        arrs = {
-            "row_off": row_off, "nnz_off": nnz_off, "n_valid": np.zeros(B, np.int32), "flags": np.zeros(B, np.uint8),
-            "usign": np.zeros(B * d, np.uint8), "avg": np.zeros(B * d, np.float32),
-            "vkind": np.zeros(max(R, 1), np.uint8), "rlo": np.zeros(max(R, 1), np.uint32),
-            "rhi": np.zeros(max(R, 1), np.uint32), "ccol": np.zeros(max(Z, 1), np.uint16),
-            "cval": np.zeros(max(Z, 1), np.float32), "cptr": np.zeros(B * (d + 1), np.uint32),
-            "cvar": np.zeros(max(Z, 1), np.uint16), "cvalc": np.zeros(max(Z, 1), np.float32),
-        }
-        st = Store(n=B, d=d, reserved=0, **{k: v.ctypes.data for k, v in arrs.items()})
+        st, arrs = host_store(n_rows, n_nnz, d)
         rc = self.lib.cave_emul_pack_large(_p(ctrs), C.c_int64(B), C.c_int64(m), C.c_int64(d), C.c_int64(nnz_cap),
                                            C.c_int64(slice_bytes), None, None, C.byref(st), C.c_int64(0), _p(status))
         assert rc == 0 and (status == 0).all(), (rc, status)
@@ -198,7 +156,7 @@ class Emul:
         self.lib.cave_emul_packed_large_slice_bytes.restype = C.c_int64
         band = band or max_rows * max_rows
         slice_bytes = int(self.lib.cave_emul_packed_large_slice_bytes(C.c_int64(d), C.c_int64(max_rows), C.c_int64(band)))
-        out = self._outs(B, d)
+        out = outs(B, d)
         rc = self.lib.cave_emul_cone_packed_large(
             C.byref(store), _p(ids), _p(pred), C.c_int64(B), C.c_int32(mode), C.c_float(sign), C.c_float(inner_ratio),
             C.c_int32(max_iter), C.c_int32(lds_bytes), C.c_int64(slice_bytes),
@@ -209,20 +167,6 @@ class Emul:
 
 
 # ---- the fused step kernel (cave_amd/csrc/cone_step.h) under the SIMT emulation
-class LiteStore(C.Structure):
-    """struct cave_lite_store (include/cave_hip.h), host arrays."""
-    _fields_ = [
-        ("n", C.c_int64), ("d", C.c_int32), ("reserved", C.c_int32),
-        ("hdr", C.c_void_p), ("usign", C.c_void_p), ("avg", C.c_void_p), ("rowptr", C.c_void_p),
-        ("ell", C.c_void_p), ("csr16", C.c_void_p), ("rl", C.c_void_p),
-    ]
-
-
-class WarmCacheC(C.Structure):
-    """struct cave_warm_cache (include/cave_hip.h), host arrays."""
-    _fields_ = [("n_entries", C.c_int64), ("key", C.c_void_p), ("theta", C.c_void_p)]
-
-
 LITE_HDR, LITE_ROWPTR, LITE_CSR_WORDS, LITE_RL = 8, 33, 768, 32  # per-slot extents of cave_lite_store
 ST_TOO_LARGE, ST_BAD_INPUT, STEP_ZERO_FAILED = 2, 3, 1
 
@@ -263,25 +207,17 @@ def warm_cache(n):
 # ballot primitives, the one-wave lite solver, the one-/two-wave band elimination, the blocked dense LDL^T --
 # compiled by g++ against a shim <hip/hip_runtime.h> in which every lane is a fiber.  TEST INFRASTRUCTURE ONLY.
 _SIMT_SRC = os.path.join(_HERE, "emul", "simt_abi.cpp")
-_SIMT_DEPS = _DEPS + [_SIMT_SRC, os.path.join(_HERE, "emul", "simt", "hip", "hip_runtime.h"), os.path.join(_HERE, "emul", "simt_solver.h"),
-                      os.path.join(_HERE, "prims", "prim_entries.h"), os.path.join(_HERE, "prims", "model_entries.h"),
-                      os.path.join(_HERE, "prims", "op_entries.h"), os.path.join(_HERE, "prims", "ipm_entries.h")] + [
-    os.path.join(_HERE, "..", "cave_amd", "csrc", n) for n in ("wave_prims.h", "ctx_wave.h", "ctx_block.h")]
 
 
 def build_simt(asan: bool = False, defines: tuple = (), tag: str = "", ops: bool = False) -> str:
     """`defines` / `tag`: a variant build (e.g. a tiny spin limit + a withheld hand-over flag) under its own name."""
     out = os.path.join(_HERE, "emul", f"_simt{tag}_asan.so" if asan else f"_simt{tag}.so")
-    newest = max(os.path.getmtime(p) for p in _SIMT_DEPS)
-    if os.path.exists(out) and os.path.getmtime(out) >= newest:
-        return out
     flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer"] if asan else ["-O2"]
     if not asan and (not defines or ops):  # the operators alone (tests/prims/op_entries.h): the plain build, or on request
         flags.append("-DCAVE_SIMT_OPS")
     cmd = ["g++", "-std=c++17", "-fPIC", "-shared", "-w", *flags, *["-D" + x for x in defines],
            "-I" + os.path.join(_HERE, "emul", "simt"), _SIMT_SRC, "-o", out]
-    subprocess.run(cmd, check=True)
-    return out
+    return _build.make(cmd, _SIMT_SRC, out)
 
 
 class Simt:
@@ -298,19 +234,11 @@ class Simt:
         self.lib.cave_simt_path_counters(out)
         return list(out)
 
-    def _outs(self, B, d):
-        return {
-            "proj": np.zeros((B, d), np.float32), "rnorm": np.zeros(B, np.float32),
-            "target": np.zeros((B, d), np.float32), "loss": np.zeros(B, np.float32),
-            "grad": np.zeros((B, d), np.float32), "status": np.zeros(B, np.int32),
-            "iters": np.zeros(B, np.int32),
-        }
-
     def cone_dense(self, ctrs, pred, mode, sign=-1.0, inner_ratio=0.2, max_iter=0, waves=1, seed=0):
         ctrs = np.ascontiguousarray(ctrs, dtype=np.float32)
         B, m, d = ctrs.shape
         pred = None if pred is None else np.ascontiguousarray(pred, dtype=np.float32)
-        out = self._outs(B, d)
+        out = outs(B, d)
         rc = self.lib.cave_simt_cone_dense(
             _p(ctrs), _p(pred), C.c_int64(B), C.c_int64(m), C.c_int64(d), C.c_int32(mode), C.c_float(sign),
             C.c_float(inner_ratio), C.c_int32(max_iter), C.c_int32(0), C.c_int32(0), C.c_int32(waves), C.c_uint64(seed),
@@ -333,18 +261,7 @@ class Simt:
                 C.c_int32(waves), C.c_uint64(seed))
         rc = self.lib.cave_simt_pack_fill(*head, None, C.c_int64(0), _p(n_rows), _p(n_nnz), _p(st1))
         assert rc == 0, rc
-        row_off = np.concatenate([[0], np.cumsum(n_rows, dtype=np.int64)]).astype(np.int64)
-        nnz_off = np.concatenate([[0], np.cumsum(n_nnz, dtype=np.int64)]).astype(np.int64)
-        R, Z = int(row_off[-1]), int(nnz_off[-1])
-        arrs = {
-            "row_off": row_off, "nnz_off": nnz_off, "n_valid": np.zeros(B, np.int32), "flags": np.zeros(B, np.uint8),
-            "usign": np.zeros(B * d, np.uint8), "avg": np.zeros(B * d, np.float32),
-            "vkind": np.zeros(max(R, 1), np.uint8), "rlo": np.zeros(max(R, 1), np.uint32),
-            "rhi": np.zeros(max(R, 1), np.uint32), "ccol": np.zeros(max(Z, 1), np.uint16),
-            "cval": np.zeros(max(Z, 1), np.float32), "cptr": np.zeros(B * (d + 1), np.uint32),
-            "cvar": np.zeros(max(Z, 1), np.uint16), "cvalc": np.zeros(max(Z, 1), np.float32),
-        }
-        st = Store(n=B, d=d, reserved=0, **{k: v.ctypes.data for k, v in arrs.items()})
+        st, arrs = host_store(n_rows, n_nnz, d)
         rc = self.lib.cave_simt_pack_fill(*head, C.byref(st), C.c_int64(0), None, None, _p(st2))
         assert rc == 0, rc
         return st, arrs, st1, st2
@@ -361,7 +278,7 @@ class Simt:
         lds = self.lib.cave_simt_packed_lds_bytes(C.c_int64(d), C.c_int32(max_rows), C.c_int32(max_nnz),
                                                   C.c_int32(3 if diet else all_pm1))
         assert lds > 0
-        out = self._outs(B, d)
+        out = outs(B, d)
         rc = self.lib.cave_simt_cone_packed(
             C.byref(store), _p(ids), _p(pred), C.c_int64(B), C.c_int32(mode), C.c_float(sign), C.c_float(inner_ratio),
             C.c_int32(max_iter), C.c_int32(lds), C.c_int32(waves), C.c_uint64(seed),
@@ -379,7 +296,7 @@ class Simt:
         band = max_rows * (max_bw + 1)
         slice_bytes = int(self.lib.cave_simt_packed_large_slice_bytes(C.c_int64(d), C.c_int64(max_rows), C.c_int64(band)))
         lds = lds_bytes or int(self.lib.cave_simt_packed_large_lds_bytes(C.c_int32(max_rows), C.c_int32(max_bw)))
-        out = self._outs(B, d)
+        out = outs(B, d)
         rc = self.lib.cave_simt_cone_packed_large(
             C.byref(store), _p(ids), _p(pred), C.c_int64(B), C.c_int32(mode), C.c_float(sign), C.c_float(inner_ratio),
             C.c_int32(max_iter), C.c_int32(lds), C.c_int32(waves), C.c_int64(slice_bytes), C.c_uint64(seed),
@@ -451,7 +368,7 @@ class Simt:
         if lds_extra is None:  # what cave_hip.hip launches the warm kernel with (step_warm_lds_extra, cone_step.h)
             lds_extra = int(self.lib.cave_simt_step_warm_lds_extra(C.c_int32(lds), C.c_int32(m_max > 0))) if warm is not None else 0
         keys = None if keys is None else np.ascontiguousarray(keys, dtype=np.int64)
-        out = self._outs(B, d)
+        out = outs(B, d)
         for k in ("proj", "target", "grad"):   # sentinels: what an instance does not write stays visible
             out[k][...] = 77.0
         out["rnorm"][...] = 77.0

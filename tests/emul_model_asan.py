@@ -12,13 +12,12 @@ import numpy as np
 import emul_lib as E
 import emul_solver_common as common
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = "model_asan_main.cpp"
 
 
 def build() -> str:
     """the stand-alone sanitizer program, by the recipe the solver emulations share (emul_solver_common.build)"""
-    return common.build(_SRC, E._SIMT_DEPS + [os.path.join(_HERE, "emul", _SRC)], "MODEL_ASAN_MAIN", asan=True)
+    return common.build(_SRC, "MODEL_ASAN_MAIN", asan=True)
 
 
 class AsanRunner:

@@ -14,35 +14,25 @@ import subprocess
 
 import numpy as np
 
+from cave_amd import _build
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 F_EVAL_COSTS = 1  # flag bit 1 of every driver: eval_costs is given
 GUARD = 8  # sentinel elements behind every guarded output
 
 
-def deps(src: str, *headers: str):
-    """the files a driver is rebuilt for: the unit, the shim, the shared driver header, the C ABI and the kernel headers"""
-    emul = os.path.join(_HERE, "emul")
-    return [os.path.join(emul, src), os.path.join(emul, "simt", "hip", "hip_runtime.h"), os.path.join(emul, "simt_solver.h"),
-            os.path.join(_HERE, "..", "include", "cave_hip.h")] + \
-        [os.path.join(_HERE, "..", "cave_amd", "csrc", h) for h in headers + ("solver_entry.h", "cone_common.h")]
-
-
-def build(src: str, dep_files, main_define: str, asan: bool = False) -> str:
+def build(src: str, main_define: str, asan: bool = False) -> str:
     """tests/emul/<src> -> the shared library for ctypes, or (`asan`) the stand-alone program under AddressSanitizer +
-    UBSan with `main_define` set; rebuilt when a file of `dep_files` is newer"""
+    UBSan with `main_define` set; rebuilt when a file it was compiled from is newer (cave_amd._build)"""
     stem = os.path.splitext(src)[0]
     out = os.path.join(_HERE, "emul", f"_{stem}_asan.exe" if asan else f"_{stem}.so")
-    newest = max(os.path.getmtime(p) for p in dep_files)
-    if os.path.exists(out) and os.path.getmtime(out) >= newest:
-        return out
     if asan:
         flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
                  "-static-libasan", "-static-libubsan", "-D" + main_define]  # runtimes linked in: the program runs as it is
     else:
         flags = ["-O2", "-fPIC", "-shared"]
-    subprocess.run(["g++", "-std=c++17", "-w", *flags, "-I" + os.path.join(_HERE, "emul", "simt"), os.path.join(_HERE, "emul", src),
-                    "-o", out], check=True)
-    return out
+    path = os.path.join(_HERE, "emul", src)
+    return _build.make(["g++", "-std=c++17", "-w", *flags, "-I" + os.path.join(_HERE, "emul", "simt"), path, "-o", out], path, out)
 
 
 def _p(a):

@@ -16,7 +16,6 @@ import emul_solver_common as common
 from emul_solver_common import F_EVAL_COSTS, _p  # noqa: F401
 
 _SRC = "simt_sp_grid.cpp"
-_DEPS = common.deps(_SRC, "sp_grid.h", "wave_prims.h")
 
 F_SOL, F_OBJ, F_EVAL, F_STATUS, F_CONES = 2, 4, 8, 16, 32
 F_ALL = 63
@@ -32,7 +31,7 @@ TABLE = (("sol", np.float32, F_SOL, lambda N, h, w: (N, n_arcs(h, w))), ("obj", 
 
 
 def build(asan: bool = False) -> str:
-    return common.build(_SRC, _DEPS, "SP_GRID_MAIN", asan)
+    return common.build(_SRC, "SP_GRID_MAIN", asan)
 
 
 class SimtSpGrid:

@@ -10,47 +10,21 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-from emul_lib import _DEPS, Store, _p
+from cave_amd import _build
+from cave_amd._lib import SparseConesC as SparseC  # struct cave_sparse_cones (include/cave_hip.h), here over host arrays
+from emul_lib import _p, host_store as empty_store
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, "emul", "emul_sparse.cpp")
 
 
-class SparseC(C.Structure):
-    """struct cave_sparse_cones (include/cave_hip.h) over host arrays."""
-    _fields_ = [("B", C.c_int64), ("m_max", C.c_int32), ("d", C.c_int32),
-                ("ent_off", C.c_void_p), ("key", C.c_void_p), ("val", C.c_void_p)]
-
-
 def build(asan: bool = False) -> str:
     out = os.path.join(_HERE, "emul", "_emul_sparse_asan.so" if asan else "_emul_sparse.so")
-    newest = max(os.path.getmtime(p) for p in _DEPS[1:] + [_SRC])
-    if os.path.exists(out) and os.path.getmtime(out) >= newest:
-        return out
     flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer"] if asan else ["-O2"]
-    subprocess.run(["g++", "-std=c++17", "-fPIC", "-shared", "-w", *flags, _SRC, "-o", out], check=True)
-    return out
-
-
-def empty_store(n_rows, n_nnz, d):
-    """Exact-fit host store for the given per-instance counts: (Store, arrays)."""
-    B = len(n_rows)
-    row_off = np.concatenate([[0], np.cumsum(n_rows, dtype=np.int64)]).astype(np.int64)
-    nnz_off = np.concatenate([[0], np.cumsum(n_nnz, dtype=np.int64)]).astype(np.int64)
-    R, Z = int(row_off[-1]), int(nnz_off[-1])
-    arrs = {
-        "row_off": row_off, "nnz_off": nnz_off, "n_valid": np.zeros(B, np.int32), "flags": np.zeros(B, np.uint8),
-        "usign": np.zeros(B * d, np.uint8), "avg": np.zeros(B * d, np.float32),
-        "vkind": np.zeros(max(R, 1), np.uint8), "rlo": np.zeros(max(R, 1), np.uint32),
-        "rhi": np.zeros(max(R, 1), np.uint32), "ccol": np.zeros(max(Z, 1), np.uint16),
-        "cval": np.zeros(max(Z, 1), np.float32), "cptr": np.zeros(B * (d + 1), np.uint32),
-        "cvar": np.zeros(max(Z, 1), np.uint16), "cvalc": np.zeros(max(Z, 1), np.float32),
-    }
-    return Store(n=B, d=d, reserved=0, **{k: v.ctypes.data for k, v in arrs.items()}), arrs
+    return _build.make(["g++", "-std=c++17", "-fPIC", "-shared", "-w", *flags, _SRC, "-o", out], _SRC, out)
 
 
 class EmulSparse:

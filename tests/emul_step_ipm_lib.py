@@ -10,11 +10,11 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-from emul_lib import _SIMT_DEPS, Simt, _p
+from cave_amd import _build
+from emul_lib import Simt, _p, outs
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, "emul", "simt_step_ipm.cpp")
@@ -22,13 +22,9 @@ _SRC = os.path.join(_HERE, "emul", "simt_step_ipm.cpp")
 
 def build(asan: bool = False) -> str:
     out = os.path.join(_HERE, "emul", "_simt_step_ipm_asan.so" if asan else "_simt_step_ipm.so")
-    newest = max(os.path.getmtime(p) for p in _SIMT_DEPS + [_SRC])
-    if os.path.exists(out) and os.path.getmtime(out) >= newest:
-        return out
     flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer"] if asan else ["-O2"]
-    subprocess.run(["g++", "-std=c++17", "-fPIC", "-shared", "-w", *flags, "-I" + os.path.join(_HERE, "emul", "simt"), _SRC,
-                    "-o", out], check=True)
-    return out
+    return _build.make(["g++", "-std=c++17", "-fPIC", "-shared", "-w", *flags, "-I" + os.path.join(_HERE, "emul", "simt"), _SRC,
+                        "-o", out], _SRC, out)
 
 
 class SimtStepIpm(Simt):
@@ -46,7 +42,7 @@ class SimtStepIpm(Simt):
             B = len(ids) if ids is not None else len(pred)
         lds = lds_bytes or self.step_lds_bytes(m_max, d)
         assert lds > 0, (m_max, d, lds)
-        out = self._outs(B, d)
+        out = outs(B, d)
         for k in ("proj", "target", "grad", "rnorm", "loss"):   # sentinels: what an instance does not write stays visible
             out[k][...] = 77.0
         out["status"][...] = -7
@@ -65,7 +61,7 @@ class SimtStepIpm(Simt):
         ctrs = np.ascontiguousarray(ctrs, dtype=np.float32)
         pred = np.ascontiguousarray(pred, dtype=np.float32)
         B, m, d = ctrs.shape
-        out = self._outs(B, d)
+        out = outs(B, d)
         rc = self.lib.cave_simt_cone_dense(
             _p(ctrs), _p(pred), C.c_int64(B), C.c_int64(m), C.c_int64(d), C.c_int32(5), C.c_float(sign), C.c_float(0.0),
             C.c_int32(max_iter), C.c_int32(nnz_cap), C.c_int32(lds_bytes), C.c_int32(waves), C.c_uint64(0),

@@ -12,11 +12,11 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-from emul_lib import _SIMT_DEPS, Simt, _p, lite_store
+from cave_amd import _build
+from emul_lib import Simt, _p, lite_store
 from emul_sparse_lib import SparseC
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -25,13 +25,9 @@ _SRC = os.path.join(_HERE, "emul", "simt_step_sparse.cpp")
 
 def build(asan: bool = False) -> str:
     out = os.path.join(_HERE, "emul", "_simt_step_sparse_asan.so" if asan else "_simt_step_sparse.so")
-    newest = max(os.path.getmtime(p) for p in _SIMT_DEPS + [_SRC])
-    if os.path.exists(out) and os.path.getmtime(out) >= newest:
-        return out
     flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer"] if asan else ["-O2"]
-    subprocess.run(["g++", "-std=c++17", "-fPIC", "-shared", "-w", *flags, "-I" + os.path.join(_HERE, "emul", "simt"), _SRC,
-                    "-o", out], check=True)
-    return out
+    return _build.make(["g++", "-std=c++17", "-fPIC", "-shared", "-w", *flags, "-I" + os.path.join(_HERE, "emul", "simt"), _SRC,
+                        "-o", out], _SRC, out)
 
 
 def sparse_of(ctrs):

@@ -17,7 +17,6 @@ from cave_amd._lib import LinSystemC
 from emul_solver_common import _p
 
 _SRC = "simt_tight_cones.cpp"
-_DEPS = common.deps(_SRC, "tight_cones.h", "wave_prims.h")
 
 TABLE = (("n_rows", np.int32, 1, lambda N, cap: (N,)), ("n_ent", np.int64, 1, lambda N, cap: (N,)),
          ("status", np.int32, 1, lambda N, cap: (N,)), ("fill_status", np.int32, 1, lambda N, cap: (N,)),
@@ -25,7 +24,7 @@ TABLE = (("n_rows", np.int32, 1, lambda N, cap: (N,)), ("n_ent", np.int64, 1, la
 
 
 def build(asan: bool = False) -> str:
-    return common.build(_SRC, _DEPS, "TIGHT_CONES_MAIN", asan)
+    return common.build(_SRC, "TIGHT_CONES_MAIN", asan)
 
 
 def c_system(s):

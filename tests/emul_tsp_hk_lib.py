@@ -13,11 +13,10 @@ from emul_solver_common import F_ALL, F_EVAL, F_EVAL_COSTS, F_OBJ, F_SOL, F_STAT
 from emul_solver_common import tsp_outputs as outputs, tsp_strip_guards as strip_guards  # noqa: F401
 
 _SRC = "simt_tsp_hk.cpp"
-_DEPS = common.deps(_SRC, "tsp_hk.h")
 
 
 def build(asan: bool = False) -> str:
-    return common.build(_SRC, _DEPS, "TSP_HK_MAIN", asan)
+    return common.build(_SRC, "TSP_HK_MAIN", asan)
 
 
 class SimtTspHk(common.SimtTsp):

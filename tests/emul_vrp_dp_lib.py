@@ -16,7 +16,6 @@ import emul_solver_common as common
 from emul_solver_common import F_EVAL_COSTS, GUARD, _p, n_edges, untouched  # noqa: F401
 
 _SRC = "simt_vrp_dp.cpp"
-_DEPS = common.deps(_SRC, "vrp_dp.h", "tsp_hk.h")
 
 F_SOL, F_OBJ, F_EVAL, F_ROUTES, F_STATUS, F_NULL_DEMANDS = 2, 4, 8, 16, 32, 64
 F_ALL = 63
@@ -27,7 +26,7 @@ NAMES = tuple(row[0] for row in TABLE)
 
 
 def build(asan: bool = False) -> str:
-    return common.build(_SRC, _DEPS, "VRP_DP_MAIN", asan)
+    return common.build(_SRC, "VRP_DP_MAIN", asan)
 
 
 def outputs(N: int, n: int, K: int, flags: int):

@@ -17,11 +17,10 @@ from emul_solver_common import F_EVAL_COSTS, GUARD, _p, n_edges, untouched  # no
 from emul_vrp_dp_lib import F_ALL, F_EVAL, F_NULL_DEMANDS, F_OBJ, F_ROUTES, F_SOL, F_STATUS, NAMES, TABLE, outputs, strip_guards  # noqa: F401
 
 _SRC = "simt_vrp_dp_wide.cpp"
-_DEPS = common.deps(_SRC, "vrp_dp_wide.h", "tsp_hk_wide.h", "vrp_dp.h", "tsp_hk.h")
 
 
 def build(asan: bool = False) -> str:
-    return common.build(_SRC, _DEPS, "VRP_DP_WIDE_MAIN", asan)
+    return common.build(_SRC, "VRP_DP_WIDE_MAIN", asan)
 
 
 class SimtVrpDpWide:

@@ -29,24 +29,20 @@ def _unit_src(unit):
 def build(verbose: bool = False) -> str:
     from concurrent.futures import ThreadPoolExecutor
 
-    from cave_amd import _lib
+    from cave_amd import _build, _lib
 
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    deps = [_SRC, os.path.join(_HERE, "prim_entries.h"), os.path.join(_HERE, "model_entries.h"), os.path.join(_HERE, "op_entries.h"), os.path.join(_HERE, "ipm_entries.h")] + [_unit_src(u) for u in _UNITS] + list(_lib._HEADERS)
-    newest = max(os.path.getmtime(p) for p in deps)
     os.makedirs(_OBJ_DIR, exist_ok=True)
     objs = [os.path.join(_OBJ_DIR, u[0] + ".o") for u in _UNITS]
-    todo = [(o, u[1], _unit_src(u)) for o, u in zip(objs, _UNITS) if not os.path.exists(o) or os.path.getmtime(o) < newest]
-    if not todo and os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(o) for o in objs):
+    todo = [(o, u[1], _unit_src(u)) for o, u in zip(objs, _UNITS) if _build.stale(o)]
+    if not todo and not _build.older(LIB_PATH, objs):
         return LIB_PATH
 
     def compile_one(job):
         obj, extra, src = job
         cmd = [hipcc, *_lib.HIPCC_FLAGS, "-I" + _lib._CSRC, "-I" + os.path.join(_ROOT, "include"), "-I" + _HERE, *extra,
                "-c", src, "-o", obj]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.run(cmd, check=True)
+        _build.run(cmd, src, obj, verbose)
 
     with ThreadPoolExecutor(max_workers=3) as ex:
         list(ex.map(compile_one, todo))
